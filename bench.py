@@ -1,14 +1,21 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X hot path (the driver's contract).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline] [--quick]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py --full [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline] [--quick]
 
 One "step" = one fused flash-attention prefill forward over the BASELINE
 config (ch06, B=8 S=4096 H=32 D=128, bf16, non-causal) on every rank.
 Flash is "replicas only" (each rank an independent replica, no collective),
 so ``value`` = N x per-replica work / max-over-ranks time (weak scaling).
 
-The same JSON line carries, as sub-objects, the other hot-path rows:
+A plain run does only that: set up, ramp, W warmup steps, K timed steps,
+the optional output dump, and the JSON line (``value``, ``ms_per_step``, the
+headline's ``roofline``).  ``--dump-outputs DIR`` writes what the last timed
+step computed as ``DIR/flash_out.npy`` (see dump_outputs).
+
+With ``--full`` the same JSON line also carries, as sub-objects, the other
+hot-path rows and comparisons (each takes launches of its own):
   gemv    ch03 decode GEMV 4096x4096 bf16 (W rotated over >256 MiB so every
           launch streams from HBM, not the 256 MiB Infinity Cache)
   decode_attn  ch02 decode attention over a [B, S, Hkv, D] KV cache (B=8,
@@ -127,6 +134,30 @@ def pmc_fields(kernel: str, kernel_ms: float | None = None) -> dict:
     if kernel_ms and cyc and busy:
         out["implied_clock_GHz"] = cyc / busy / (kernel_ms * 1e6)
     return out
+
+
+DUMP_ROWS = 32768  # of B*H*S = 1,048,576 output rows; x D=128 fp32 = 16 MiB
+DUMP_SEED = 4321
+
+
+def dump_outputs(path: str, o: torch.Tensor, world: int, rank: int) -> None:
+    """``--dump-outputs DIR``: what the timed step's caller receives, the flash
+    output ``o`` [B, H, S, D] as the last timed step left it, written as
+    ``DIR/flash_out.npy`` (``flash_out_rank<r>.npy`` per rank when N > 1) in
+    float32.  The whole tensor is 512 MiB as fp32, so a fixed sample is kept:
+    DUMP_ROWS whole rows (one (b, h, s) position, all D values each) drawn
+    without replacement by numpy's RandomState(DUMP_SEED), in ascending row
+    order.  Inputs are seeded, so two builds run with the same arguments
+    write comparable files."""
+    import numpy as np
+    rows = o.reshape(-1, o.shape[-1])
+    idx = np.sort(np.random.RandomState(DUMP_SEED).choice(rows.shape[0], min(DUMP_ROWS, rows.shape[0]),
+                                                          replace=False))
+    sample = rows[torch.from_numpy(idx).to(o.device)].float().cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    name = "flash_out.npy" if world == 1 else f"flash_out_rank{rank}.npy"
+    np.save(os.path.join(path, name), sample)
+    log(f"[bench] wrote {os.path.join(path, name)} {sample.shape} {sample.dtype}")
 
 
 def calibrate() -> dict:
@@ -751,14 +782,26 @@ def main():
     # untimed launches first: the first ~10 flash launches in a process run
     # 2-15 % slower (clock / TLB warm-up; rocprof trace in profiles/r02/final)
     ap.add_argument("--warmup", type=int, default=30)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--quick", action="store_true", help="skip gemm/tp/cpu legs")
-    ap.add_argument("--with-decode", action="store_true", help="with --quick: keep the decode leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the unramped protocol, causal, calibration, torch SDPA, other "
+                         "dtypes, gemv, decode, gemm, tp gemm, decode step, ch05 demo and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's output (a fixed sample, float32) as DIR/flash_out.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU legs")
+    ap.add_argument("--quick", action="store_true", help="with --full: skip gemm/tp/cpu legs")
+    ap.add_argument("--with-decode", action="store_true", help="with --full --quick: keep the decode leg")
     ap.add_argument("--flash-only", action="store_true",
-                    help="only the headline flash step (clean rocprof stats for that kernel)")
+                    help="with --full: only the headline flash step and the unramped protocol "
+                         "(clean rocprof stats for that kernel)")
     ap.add_argument("--selftest", action="store_true",
                     help="CPU rehearsal of the multi-rank launch (gloo, a CPU matmul step; not a result)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        if args.quick or args.with_decode or args.no_cpu_baseline:
+            log("[bench] --quick / --with-decode / --no-cpu-baseline trim a --full run; a plain run has no such legs")
+        args.flash_only = True  # a plain run: the headline alone
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # one process asked for N GPUs: start the N ranks (nothing has touched the GPU yet)
@@ -804,26 +847,27 @@ def main():
     step = lambda: pli_hip.flash_attn_fwd(q, k, v, out=o)  # noqa: E731
     flops_step = 4 * B * H * S * S * D
 
-    # the driver's protocol first, as asked: W warmup steps, then K steps
-    # timed (barrier + synchronize both sides) -- reported as `unramped`
-    # beside the headline (the headline below follows a 1 s ramp)
-    for _ in range(args.warmup):
-        step()
-    torch.cuda.synchronize()
-    route = pli_hip.last_route()  # the kernel the timed step launches (pli_last_route)
-    if world > 1:
-        dist.barrier()
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t_u = time.perf_counter()
-    ev0.record(stream)
-    for _ in range(args.steps):
-        step()
-    ev1.record(stream)
-    torch.cuda.synchronize()
-    unramped = {"wall_ms_per_step": (time.perf_counter() - t_u) / args.steps * 1e3,
-                "kernel_ms": ev0.elapsed_time(ev1) / args.steps,
-                "note": "the driver's --warmup W then --steps K on a fresh process (no ramp); rank-local"}
-    unramped["TFLOP/s"] = 4 * B * H * S * S * D / (unramped["kernel_ms"] * 1e-3) / 1e12
+    # --full: the bare protocol first, W warmup steps, then K steps timed
+    # (barrier + synchronize both sides) -- reported as `unramped` beside
+    # the headline (the headline below follows a 1 s ramp)
+    unramped = None
+    if args.full:
+        for _ in range(args.warmup):
+            step()
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t_u = time.perf_counter()
+        ev0.record(stream)
+        for _ in range(args.steps):
+            step()
+        ev1.record(stream)
+        torch.cuda.synchronize()
+        unramped = {"wall_ms_per_step": (time.perf_counter() - t_u) / args.steps * 1e3,
+                    "kernel_ms": ev0.elapsed_time(ev1) / args.steps,
+                    "note": "--warmup W then --steps K on a fresh process (no ramp); rank-local"}
+        unramped["TFLOP/s"] = 4 * B * H * S * S * D / (unramped["kernel_ms"] * 1e-3) / 1e12
     # device ramp: a fresh process starts from an idle clock state, and a
     # short --warmup (the driver runs W = 5, 8 ms) leaves part of the clock
     # ramp inside the timed steps; run the step back to back for ramp_ms of
@@ -838,6 +882,8 @@ def main():
         torch.cuda.synchronize()
     for _ in range(args.warmup):
         step()
+    torch.cuda.synchronize()
+    route = pli_hip.last_route()  # the kernel the timed step launches (pli_last_route)
 
     def barrier():
         if world > 1:
@@ -862,6 +908,8 @@ def main():
     wall_max = t.item()
     value = world * flops_step * args.steps / wall_max / 1e12
     achieved = flops_step / (kernel_ms * 1e-3) / 1e12
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, o, world, rank)  # before any --full leg reuses `o`
 
     extra = {}
     measured_roof = {}
@@ -965,7 +1013,6 @@ def main():
         "warmup": args.warmup,
         "ramp": {"ms": ramp_ms, "launches": n_ramp,
                  "note": "untimed back-to-back steps before the warmup (idle clock state of a fresh process)"},
-        "unramped": unramped,
         "ms_per_step": wall_max / args.steps * 1e3,
         "higher_is_better": True,
         "scaling": "weak",
@@ -986,6 +1033,8 @@ def main():
                      "kernel": FLASH_KERNEL, "route": route, "algorithmic_flops": flops_step,
                      "kernel_ms": kernel_ms, **measured_roof},
     }
+    if unramped is not None:
+        result["unramped"] = unramped
     if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.quick:
         log("[bench] cpu baseline")
         result["cpu_baseline"] = cpu_baseline()

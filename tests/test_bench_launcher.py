@@ -69,6 +69,46 @@ def test_headline_summary_and_tail_order():
     assert s["n_gpus"] is None and "tp_allreduce_us" not in s  # (a one-GPU record)
 
 
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_dump_outputs_is_a_fixed_sample_of_rows(tmp_path, monkeypatch):
+    """--dump-outputs: float32, whole rows of the tensor in ascending row
+    order, the same rows on every call; all rows when there are no more than
+    DUMP_ROWS; the bench shape's dump stays under the 64 MB limit."""
+    import numpy as np
+    import torch
+    bench = _bench_module()
+    assert bench.DUMP_ROWS * bench.D * 4 <= 64 * 10 ** 6 and bench.DUMP_ROWS <= bench.B * bench.H * bench.S
+    o = torch.randn(2, 3, 50, 8, generator=torch.Generator().manual_seed(5)).to(torch.bfloat16)
+    bench.dump_outputs(str(tmp_path / "all"), o, 1, 0)
+    a = np.load(tmp_path / "all" / "flash_out.npy")
+    assert a.dtype == np.float32
+    np.testing.assert_array_equal(a, o.float().reshape(-1, 8).numpy())
+    monkeypatch.setattr(bench, "DUMP_ROWS", 16)
+    bench.dump_outputs(str(tmp_path / "s1"), o, 1, 0)
+    bench.dump_outputs(str(tmp_path / "s2"), o.clone(), 2, 1)
+    s1 = np.load(tmp_path / "s1" / "flash_out.npy")
+    s2 = np.load(tmp_path / "s2" / "flash_out_rank1.npy")
+    assert s1.shape == (16, 8) and s1.dtype == np.float32
+    np.testing.assert_array_equal(s1, s2)
+    rows = [int(np.flatnonzero((a == r).all(axis=1))[0]) for r in s1]  # each sampled row is a row of o
+    assert rows == sorted(set(rows))
+
+
+def test_headline_summary_of_a_plain_run():
+    """Without --full the record has the headline only: summary still forms."""
+    s = _bench_module().headline_summary({"roofline": {"achieved": 1390.0, "frac": 0.552, "kernel_ms": 1.58},
+                                          "n_gpus": 1, "ranks_seen": 1, "backend": None})
+    assert s == {"flash_TFLOP/s": 1390.0, "flash_frac": 0.552, "flash_kernel_ms": 1.58,
+                 "n_gpus": 1, "ranks_seen": 1, "backend": None}
+
+
 def test_headline_summary_multi_rank_keys():
     """N > 1 (verdict r5 item 5): the rank count, backend and the TP
     all-reduce leg (ch09 RowParallelLinear over RCCL) land in `summary`"""

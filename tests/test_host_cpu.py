@@ -173,8 +173,9 @@ def test_cpu_online_softmax_vs_golden():
     np.testing.assert_allclose(d.numpy(), g["x4_d"], rtol=1e-10)
 
 
-def test_triton_name_is_the_hip_gemm_on_cpu():
+def test_triton_name_is_the_hip_gemm_on_cpu(monkeypatch):
     from ch05 import tiled_matmul, triton_matmul
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)  # the host behaviour, on any machine
     a, b = torch.randn(8, 16), torch.randn(16, 4)
     torch.testing.assert_close(triton_matmul(a, b), a @ b)
     torch.testing.assert_close(triton_matmul(a, b, 32, 32, 32), tiled_matmul(a, b))

@@ -4,8 +4,8 @@ kernel trace of the same run.
 
     python tools/trace_check.py <run_kernel_trace.csv> <bench json> [warmup] [steps]
 
-bench.py launches `warmup` then `steps` non-causal flash steps first (the
-timed region), then the causal extras with the same kernel instantiation, so
+bench.py --full launches `warmup` then `steps` non-causal flash steps first (its
+unramped protocol), then the ramp, the headline and the extras with the same kernel instantiation, so
 the stats file's single average mixes both; this takes the timed dispatches
 by launch order.
 """
