@@ -52,7 +52,7 @@ class FlashAttentionConfig:
 # generated attn_fwd_v13 family (v13 / v13c / v13h / v13hc / v13r / v13rc /
 # the _d64 bodies) -- 256-row blocks of 4 waves x 64 rows, 64-key tiles, a
 # 5-slot LDS ring two tiles ahead; only other head dims and Nk <= 64 fall
-# back to attn_fwd_v12 / v10 / v7 (csrc/flash_v13.hip attn_v13_ok).  Non-causal
+# back to attn_fwd_v12 / v10 / v7 (csrc/flash_plan.h plan_flash).  Non-causal
 # D = 64 where B H ceil(Nq / 512) fills the CUs: attn_fwd_pp64 (512-row blocks
 # of 8 waves, a 6-slot ring four tiles ahead; tools/v14/pp64.py)
 HIP_TILING = {"block_q": 256, "block_k": 64, "num_warps": 4, "num_stages": 5}

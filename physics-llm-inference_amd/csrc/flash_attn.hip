@@ -26,17 +26,12 @@
 // Generic kernel (fp32, or any head_dim <= 128, or unaligned operands):
 // LDS-tiled VALU kernel with the same online recurrence, fp32 accumulate.
 #include <cmath>
-#include <type_traits>
 
 #include "flash_v7.h"
 #include "pli_common.h"
 
 namespace pli {
 namespace {
-
-struct AttnStrides {
-    int64_t qb, qh, qn, kb, kh, kn, vb, vh, vn, ob, oh, on;
-};
 
 constexpr int KT = 64;  // keys per LDS tile
 constexpr int QW = 32;  // query rows per wave
@@ -95,7 +90,7 @@ template <typename T, int D, int NW, bool LAZY, int OPT = 0, int KTL = KT>
 __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_v2(
     const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
     const uint16_t* __restrict__ v, uint16_t* __restrict__ o, int H, int group,
-    int Nq, int Nk, AttnStrides st, float c, int causal, int qblocks,
+    int Nq, int Nk, V7Strides st, float c, int causal, int qblocks,
     int nblocks) {
     using L = PadLayout<D, KTL>;
     constexpr int NS = KTL / 32;        // 32-key sub-tiles per tile
@@ -404,7 +399,7 @@ constexpr int GQ = 32, GK = 64, GDMAX = 128;
 template <typename T>
 __global__ __launch_bounds__(256) void attn_fwd_generic(
     const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v,
-    T* __restrict__ o, int H, int group, int Nq, int Nk, int D, AttnStrides st,
+    T* __restrict__ o, int H, int group, int Nq, int Nk, int D, V7Strides st,
     float scale, int causal, int qblocks) {
     extern __shared__ __attribute__((aligned(16))) float gsm[];
     const int ldq = D + 1;
@@ -494,241 +489,55 @@ __global__ __launch_bounds__(256) void attn_fwd_generic(
     }
 }
 
-// Kernel variants behind the same ABI (pli_flash_attn_fwd_variant, tuning /
-// A-B runs; every one is parity-tested, the default at the full bench size):
-//  21: attn_fwd_v2, 8 waves, permlane row max + defer-max (THR 8, log2) +
-//      rounded-P row sum by v_dot2c (the round-1 default, kept as baseline)
-//  50: attn_fwd_v7 (flash_v7.hip): Q prescaled by scale*log2(e) (bf16-rounded)
-//      with -m as the first QK^T MFMA's C operand, speculative exp2, row sum
-//      on the matrix core; register-staged K/V, one tile ahead
-//  51: attn_fwd_v7 with exact scaling (p = exp2(fma(s, c, -m)))
-//  54: attn_fwd_v10: v7's body, K/V by LDS-DMA two tiles ahead into a 3-deep
-//      ring of XOR-swizzled images (D = 128; other head dims take v7), prescaled
-//  55: attn_fwd_v10 with exact scaling -- the DEFAULT (D = 128; D = 64 -> 51)
-//  60: attn_fwd_v10 exact with 4-wave workgroups (128 rows), two per CU, a
-//      2-slot ring one tile ahead -- the CAUSAL default (D = 128; D = 64 -> 51)
-// The round-1 experiments (XOR-swizzled v1, staggered v3, pipelined v4/v5,
-// 16x16x32 v6, ping-pong, segmented, one-wave-per-SIMD w4/w4p) and the
-// round-2 ones that lost (in-wave pipelined v8, one-wave-per-SIMD v9, a
-// two-barrier stagger with s_setprio, a half-tile lag on a 4-deep ring, the
-// 4-wave one-wave-per-SIMD software-pipelined v11: 719-760 TF, static
-// s_setprio 1 on waves 4-7: 1088 vs 1088 TF, the DMA pieces issued between
-// the PV MFMAs: 1035 vs 1061 TF, two 64-key tiles per barrier on a 4-slot
-// ring: 1054 vs 1054 TF, causal 850 vs 844) are
-// not in the library; their measurements are in DESIGN.md 3.1.
-//  70: attn_fwd_v12 (flash_v12.hip): 4 waves x 64 rows, one wave per SIMD,
-//      O / Q / K fragments in literally named accumulator registers, a
-//      hand-placed stream (one exp per MFMA gap), 5-slot LDS ring; bitwise
-//      equal to 55 (bf16, D = 128, non-causal, Nk % 64 == 0; else 55)
-//  71: attn_fwd_v12 persistent (one workgroup per CU walking its XCD's
-//      blocks, the K/V stream and the next block's Q across block seams) --
-//      the DEFAULT where 70 applies (1181 vs 1082 TF/s for 55)
-//  73 / 74: attn_fwd_v12 causal (bottom-right, Nq <= Nk), one block per
-//      workgroup heaviest first / persistent with the pair walk
-//  72: variant 71 with the defer-max threshold at 0 (a rescale whenever a
-//      tile raises a row's max): tests only, the threshold sweep of
-//      cdna_hip_programming.md rule 26 (72 and 71 agree to rounding)
-//  80: attn_fwd_v13 (flash_v13.hip): 4 waves x 64 rows, one wave per SIMD,
-//      v_mfma_f32_16x16x32_bf16 (the shape the chip clocks higher under load),
-//      one generated instruction stream (tools/gen_flash_v13.py), persistent;
-//      defer-max on P itself (D = 128 / 64, non-causal, Nk % 64 == 0 and Nk
-//      >= 128, or any Nk > 64 on the ragged bodies attn_fwd_v13r / v13hr --
-//      round 5; else 71); fp16 inputs run the same program on the f16 MFMA
-//      (attn_fwd_v13h / v13hc, since round 5; before: 71 -> 55 / 60)
-//  81: variant 80 with one block per workgroup
-//  82: variant 80 with mu = max * c (P = 1 at the max, so every row's l >= 1
-//      and the rare path runs at every tile): tests only
-//  83 / 84: attn_fwd_v13c causal (bottom-right, Nq <= Nk; any diagonal
-//      offset -- virtual rows -- and ragged Nk -- attn_fwd_v13rc -- since
-//      round 5): 83 persistent (the pair walk where it tiles the grid), 84 one
-//      block per workgroup heaviest first; 85 = 83 with mu = max * c
-// default since round 4: attn_fwd_v13 (80), 1388 vs 1242 TF/s for v12 (71)
-// at B8 S4096 H32 D128 in the same process (profiles/r04/flash/ab.log); where
-// v13 does not apply (D not 64 / 128, Nk <= 64) it routes to 71 / 74.
-// Since round 6 the default is 88: attn_fwd_pp64 / pp64h (86) for head dim 64
-// non-causal where its blocks fill the chip (two waves per SIMD in ping-pong;
-// bitwise v13's D = 64 result, 1259 vs 1104 TF/s at B8 H32 S4096 D64 in the
-// same process, profiles/r06/pp64/), v13 (80) for everything else
-constexpr int kDefaultVariant = 88;
-// v13's mu = row max * c + PLI_V13_MUOFF (log2 units): P <= 2^-MUOFF right
-// after a max is taken and a tile takes the rescale path once some row's sum l
-// reaches 1 (since round 5; a row max grown by about MUOFF - log2 Nk -- the P
-// >= 2 bit test of round 4 fired at MUOFF + 1).  62 (since round 4; was 7, the THR 8 of v10 /
-// v12): P stays a normal bf16 / fp32 down to 2^-126, so only scores 64+ log2
-// units under the row max flush to 0 (weight < 2^-64), and the rescale path
-// all but vanishes where the scaled scores spread wide -- B8 H32 S4096, N(0,1)
-// inputs, TF/s 7 -> 62: scale 1.0 590 -> 1368 (causal 452 -> 1172), 0.25
-// 1150 -> 1386 (891 -> 1167), 1/sqrt(128) 1377 -> 1390 (1166 -> 1167)
-// (profiles/r04/scale/ab_muoff.jsonl)
-#ifndef PLI_V13_MUOFF
-#define PLI_V13_MUOFF 62.f
-#endif
-// Range of V this offset supports (bf16 v13; the v12 / v7 / v10 bf16 bodies'
-// threshold 64 mirrors it): P is about 2^-62 at a row's max, so P * V stays a
-// normal fp32 down to |V| ~ 2^-64 and products below flush gradually
-// (subnormal fp32 keeps 2^-149 absolute); on the other side P <= 1 (v13's
-// clamp) and O <= l max|V|, so any finite bf16 V is safe.  Exercised at |V|
-// scaled by 2^-60 and 2^50 against f64 (tests/test_gpu_flash_v13.py
-// test_v13_v_range, variants 80 / 83 / 71 / 55).
-// fp16 (attn_fwd_v13h / v13hc, since round 5): fp16 P is normal down to 2^-14
-// and zero below 2^-24, so the offset stays small -- P <= 2^-4 when a max is
-// taken, the rescale path once a row max grows by 5 (some P >= 2, the bit-14
-// test), scores 20+ log2 units under the running estimate flush to 0 (weight
-// < 2^-20 of the row's largest: at most Nk * 2^-20 of the sum in total)
-//
-// Round 6: that flush is what limits fp16 at long context.  On an
-// attention-sink row (one dominant key, the rest d log2 units under it) the
-// weights just above 2^-(24 - offset) are quantised to a few subnormal steps
-// and those below it dropped, so the worst-case error grows with Nk * 2^offset:
-// a numpy model of the packing gives, offset 4 / 3 / 2 / 1 (torch's fp16 SDPA
-// in brackets), Nk 4096 2.9e-3 / 1.5e-3 / 7.5e-4 / 1.9e-4 (9.3e-4), 8192
-// 9.6e-3 / 2.5e-3 / 1.5e-3 / 3.4e-4 (1.3e-3), 16384 1.1e-2 / 5.9e-3 / 3.2e-3 /
-// 6.9e-4 (1.5e-3), 32768 2.6e-2 / 1.1e-2 / 5.6e-3 / 1.5e-3 (1.5e-3), 65536
-// 4.6e-2 / 2.7e-2 / 1.1e-2 / 3.1e-3 (2.7e-3).  So the offset
-// falls by one per doubling of Nk past 4096 (floor 1): the worst case stays
-// at ~3e-3, within ~2x of torch's, and the bench's Nk 4096 keeps offset 4.
-// A smaller offset takes the rescale path more often (B8 S4096: 4 / 2 / 0 at
-// 1308 / 1138 / 662 TF/s; B1 S32768: 1393 / 1324 / 1035).
-#ifndef PLI_V13_MUOFF_F16
-#define PLI_V13_MUOFF_F16 4.f
-#endif
-static float v13_muoff_f16(int Nk) {
-    float m = PLI_V13_MUOFF_F16;
-    for (int64_t n = 4096; n < Nk && m > 1.f; n *= 2) m -= 1.f;
-    return m;
-}
-// causal: attn_fwd_v12 causal (74; one block per workgroup where the
-// persistent pair walk does not tile the shape), 60 where v12 does not apply
-// (fp16, D != 128, Nq > Nk, Nk % 64): B8 S4096 H32 D128 bf16 1002 (74, the
-// first rotation walk) vs 945 (60) TF/s, B2 S8192 1098 vs 1013, B32 S2048 867
-// vs 830 (profiles/r03/flash/ab_causal.log); the pair walk: 1049 at B8 S4096,
-// 1154 at B2 S8192, 1223 at B1 H64 S16384 (ab_causal_pair.log)
-// causal default since round 4: attn_fwd_v13c (83), 1210 vs 1058 TF/s for
-// 74 (profiles/r04/flash/ab_causal.log); since round 5 83 takes any diagonal
-// offset, ragged Nk, fp16 and D 64 too; Nk <= 64 -> 74 where v12 applies (bf16,
-// D 128, Nk = 64), else 60 (so also other D and Nq > Nk)
-constexpr int kDefaultCausalVariant = 83;
-
+// attn_fwd_v2 (variant 21), the end of plan_flash's chain; a variant number no
+// stage of the chain knows ends here too, as an error
 template <typename T, int D>
-int launch_mfma(const void* q, const void* k, const void* v, void* o, int B, int H,
-                int group, int Nq, int Nk, const AttnStrides& st, float scale,
-                int causal, hipStream_t stream, int variant) {
-    // the MFMA bodies' defer-max sets m from the raw score max times c =
-    // scale*log2(e): only for c > 0 is that the row's largest scaled score
-    // (c <= 0 would make exp2(s*c - m) >= 1 and overflow); zero or negative
-    // scales never get here (the generic kernel's max is of the scaled scores).
-    // Only the prescaled variants 50 / 54 multiply Q by c in the 16-bit input
-    // type (so c > 1 could overflow fp16 Q): they alone need c <= 1; v13, v12
-    // and the exact 51 / 55 / 60 apply c by fma in fp32 (any c > 0).
-    const float c_log2 = scale * 1.4426950408889634f;
-    const bool c_ok = c_log2 > 0.f && c_log2 <= 1.f;
-    // the exact bodies (v12 70-74, v7 / v10 51 / 55 / 60) apply c by fma to
-    // the fp32 scores: any c > 0; only the prescaled ones (50 / 54) need c <= 1
-    const bool c_pos = c_log2 > 0.f;
-    // 86: attn_fwd_pp64 / pp64h (causal: pp64c / pp64hc) where it applies
-    // (head dim 64, bf16 / fp16, Nk % 64 == 0; causal with Nq and Nk - Nq
-    // multiples of 64; tools/v14/pp64.py), else the default v13 form; 87: the
-    // same with the rescale path at every tile (muoff 0 / -1, tests)
-    // 88 (the default since round 6): 86 where its 512-row blocks fill the
-    // chip (B H ceil(Nq / 512) >= the CU count), else 80 -- below that v13's
-    // 256-row blocks spread the same work over twice as many CUs (B2 H8 S512:
-    // 61 vs 85 TF/s on pp64, profiles/r06/pp64/)
-    // (causal stays on v13c: pp64c -- the causal pp64 forms, one block per
-    // workgroup heaviest first -- measured 725 vs 946 TF/s bf16, 802 vs 941
-    // fp16 at B8 H32 S4096 D64, profiles/r06/pp64/ab9_causal_*.jsonl)
-    if (variant == 88) {
-        const bool fill = (int64_t)B * H * cdiv(Nq, 512) >= cu_count(stream);
-        variant = causal ? 83 : fill ? 86 : 80;
-    }
-    if (variant == 86 || variant == 87) {
-        const bool bf = std::is_same<T, bf16_t>::value;
-        const V7Strides s7{st.qb, st.qh, st.qn, st.kb, st.kh, st.kn, st.vb, st.vh, st.vn, st.ob, st.oh, st.on};
-        if (attn_pp64_ok(D, !bf, causal != 0, Nq, Nk) && attn_v13_ok(D, bf ? 1 : 0, causal, Nq, Nk, s7) &&
-            c_log2 > 0.f && H < (1 << 16))
-            return launch_attn_v13(q, k, v, o, B, H, group, Nq, Nk, s7, scale, stream, true,
-                                   variant == 87 ? (bf ? 0.f : -1.f) : bf ? PLI_V13_MUOFF : v13_muoff_f16(Nk),
-                                   nullptr, causal != 0, !bf, D, true);
-        variant = causal ? (variant == 87 ? 85 : 83) : variant == 87 ? 82 : 80;
-    }
-    if (variant >= 80 && variant <= 85) {
-        const bool bf = std::is_same<T, bf16_t>::value;
-        const bool cv = variant >= 83;  // the causal forms
-        const V7Strides s7{st.qb, st.qh, st.qn, st.kb, st.kh, st.kn, st.vb, st.vh, st.vn, st.ob, st.oh, st.on};
-        // v13 scales in fp32 (s * c - mu by v_fma): any c > 0 (scale = 1 etc.)
-        // the rare-path sweep (82 / 85): bf16's l check trips at every tile with
-        // mu = max * c (P = 1 at the max), fp16's P-bit check with mu = max * c - 1
-        const float sweep = bf ? 0.f : -1.f;
-        if (cv == (causal != 0) && attn_v13_ok(D, bf ? 1 : 0, causal, Nq, Nk, s7) && c_log2 > 0.f && H < (1 << 16))
-            return launch_attn_v13(q, k, v, o, B, H, group, Nq, Nk, s7, scale, stream, variant != 81 && variant != 84,
-                                   (variant == 82 || variant == 85) ? sweep : bf ? PLI_V13_MUOFF : v13_muoff_f16(Nk),
-                                   nullptr, causal != 0, !bf, D);
-        variant = causal ? 74 : 71;
-    }
-    if (variant == 70 || variant == 71 || variant == 72) {
-        const bool bf = std::is_same<T, bf16_t>::value;
-        if (attn_v12_ok(D, bf ? 1 : 0, causal, Nk) && c_pos) {
-            const V7Strides s7{st.qb, st.qh, st.qn, st.kb, st.kh, st.kn,
-                               st.vb, st.vh, st.vn, st.ob, st.oh, st.on};
-            return launch_attn_v12(q, k, v, o, B, H, group, Nq, Nk, s7, scale, stream, variant != 70,
-                                   variant == 72 ? 0.f : 64.f);
-        }
-        variant = causal ? 60 : 55;
-    }
-    if (variant == 73 || variant == 74) {
-        const bool bf = std::is_same<T, bf16_t>::value;
-        if (causal && attn_v12_ok(D, bf ? 1 : 0, 0, Nk) && Nq <= Nk && c_pos) {
-            const V7Strides s7{st.qb, st.qh, st.qn, st.kb, st.kh, st.kn,
-                               st.vb, st.vh, st.vn, st.ob, st.oh, st.on};
-            return launch_attn_v12(q, k, v, o, B, H, group, Nq, Nk, s7, scale, stream, variant == 74, 64.f, true);
-        }
-        variant = causal ? 60 : 55;
-    }
-    if (variant == 50 || variant == 51 || variant == 54 || variant == 55 || variant == 60) {
-        if (variant == 50 || variant == 54 ? c_ok : c_pos) {
-            const V7Strides s7{st.qb, st.qh, st.qn, st.kb, st.kh, st.kn,
-                               st.vb, st.vh, st.vn, st.ob, st.oh, st.on};
-            return launch_attn_v7(q, k, v, o, B, H, group, Nq, Nk, D, s7, scale, causal,
-                                  std::is_same<T, bf16_t>::value ? 1 : 0, stream, variant - 50);
-        }
-        variant = 21;
-    }
+int launch_v2(const FlashCall& f, const FlashPlan& plan, const void* q, const void* k, const void* v, void* o,
+              hipStream_t stream) {
     constexpr int nw = 8;
-    const int qblocks = cdiv(Nq, nw * QW);
-    const int64_t nb = (int64_t)B * H * qblocks;
+    const int qblocks = cdiv(f.Nq, nw * QW);
+    const int64_t nb = (int64_t)f.B * f.H * qblocks;
     PLI_REQUIRE(nb < (1ll << 31), "pli_flash_attn_fwd: grid too large");
-    const float c = scale * 1.4426950408889634f;  // fold log2(e) into the scale
-    const auto* qq = (const uint16_t*)q;
-    const auto* kk = (const uint16_t*)k;
-    const auto* vv = (const uint16_t*)v;
-    auto* oo = (uint16_t*)o;
-    const dim3 grid((unsigned)nb), block(nw * 64);
-    switch (variant) {
-        case 21:
-            hipLaunchKernelGGL((attn_fwd_v2<T, D, 8, true, 13>), grid, block, 0, stream, qq, kk, vv, oo, H,
-                               group, Nq, Nk, st, c, causal, qblocks, (int)nb);
-            break;
-        default:
-            set_error("pli_flash_attn_fwd: unknown variant %d", variant);
-            return PLI_EINVAL;
-    }
+    PLI_REQUIRE(plan.family == FlashFamily::v2, "pli_flash_attn_fwd: unknown variant %d", plan.variant);
+    const float c = f.scale * 1.4426950408889634f;  // fold log2(e) into the scale
+    hipLaunchKernelGGL((attn_fwd_v2<T, D, nw, true, 13>), dim3((unsigned)nb), dim3(nw * 64), 0, stream,
+                       (const uint16_t*)q, (const uint16_t*)k, (const uint16_t*)v, (uint16_t*)o, f.H, f.group, f.Nq,
+                       f.Nk, f.st, c, (int)f.causal, qblocks, (int)nb);
     return launch_status("attn_fwd_v2");
 }
 
+// the MFMA families of a plan (flash_plan.h plan_flash holds the routing rules)
+int launch_mfma(const FlashCall& f, const FlashPlan& plan, const void* q, const void* k, const void* v, void* o,
+                hipStream_t stream) {
+    switch (plan.family) {
+        case FlashFamily::pp64:
+        case FlashFamily::v13:
+            return launch_attn_v13(f, plan, q, k, v, o, stream);
+        case FlashFamily::v12:
+            return launch_attn_v12(f, plan, q, k, v, o, stream);
+        case FlashFamily::v7:
+            return launch_attn_v7(f, plan, q, k, v, o, stream);
+        default:
+            if (!f.fp16)
+                return f.D == 128 ? launch_v2<bf16_t, 128>(f, plan, q, k, v, o, stream)
+                                  : launch_v2<bf16_t, 64>(f, plan, q, k, v, o, stream);
+            return f.D == 128 ? launch_v2<f16_t, 128>(f, plan, q, k, v, o, stream)
+                              : launch_v2<f16_t, 64>(f, plan, q, k, v, o, stream);
+    }
+}
+
 template <typename T>
-int launch_generic(const void* q, const void* k, const void* v, void* o, int B, int H,
-                   int group, int Nq, int Nk, int D, const AttnStrides& st, float scale,
-                   int causal, hipStream_t stream) {
-    const int qblocks = cdiv(Nq, GQ);
-    const int64_t nb = (int64_t)B * H * qblocks;
+int launch_generic(const FlashCall& f, const void* q, const void* k, const void* v, void* o, hipStream_t stream) {
+    const int D = f.D, qblocks = cdiv(f.Nq, GQ);
+    const int64_t nb = (int64_t)f.B * f.H * qblocks;
     PLI_REQUIRE(nb < (1ll << 31), "pli_flash_attn_fwd: grid too large");
     const size_t lds = sizeof(float) * ((size_t)GQ * (D + 1) + (size_t)GK * (D + 1) +
                                         (size_t)GK * D + (size_t)GQ * (GK + 1));
     hipLaunchKernelGGL((attn_fwd_generic<T>), dim3((unsigned)nb), dim3(256), lds, stream,
-                       (const T*)q, (const T*)k, (const T*)v, (T*)o, H, group, Nq, Nk, D, st,
-                       scale, causal, qblocks);
+                       (const T*)q, (const T*)k, (const T*)v, (T*)o, f.H, f.group, f.Nq, f.Nk, D, f.st,
+                       f.scale, (int)f.causal, qblocks);
     return launch_status("attn_fwd_generic");
 }
-
 
 }  // namespace
 }  // namespace pli
@@ -753,40 +562,22 @@ extern "C" int pli_flash_attn_fwd_variant(const void* q, const void* k, const vo
     // keys -> O = 0 (the generic kernel reads no K / V)
     if (batch == 0 || n_q == 0) return PLI_OK;
     PLI_REQUIRE(q && o && strides && (n_kv == 0 || (k && v)), "pli_flash_attn_fwd: null pointer");
-    const AttnStrides st{strides[0], strides[1], strides[2], strides[3], strides[4], strides[5],
-                         strides[6], strides[7], strides[8], strides[9], strides[10], strides[11]};
-    const int group = heads / kv_heads;
     hipStream_t s = (hipStream_t)stream;
-    // n_kv == 0 (softmax over no keys) goes to the generic kernel, which
-    // defines the output as zeros.
-    bool vec = (dtype == PLI_BF16 || dtype == PLI_F16) && (head_dim == 64 || head_dim == 128) &&
-               aligned16(q) && aligned16(k) && aligned16(v) && aligned16(o) && n_kv > 0 &&
-               scale > 0.f;  // the MFMA kernels' running max assumes a positive scale (launch_mfma)
-    for (int i = 0; i < 12; ++i) {
-        const bool inner = (i % 3) == 2;
-        vec = vec && (strides[i] % 8 == 0) && (!inner || strides[i] >= head_dim);
-    }
-    if (vec) {
-        if (variant < 0) variant = causal ? kDefaultCausalVariant : kDefaultVariant;
-        if (dtype == PLI_BF16)
-            return head_dim == 128 ? launch_mfma<bf16_t, 128>(q, k, v, o, batch, heads, group, n_q, n_kv, st, scale, causal, s, variant)
-                                   : launch_mfma<bf16_t, 64>(q, k, v, o, batch, heads, group, n_q, n_kv, st, scale, causal, s, variant);
-        return head_dim == 128 ? launch_mfma<f16_t, 128>(q, k, v, o, batch, heads, group, n_q, n_kv, st, scale, causal, s, variant)
-                               : launch_mfma<f16_t, 64>(q, k, v, o, batch, heads, group, n_q, n_kv, st, scale, causal, s, variant);
-    }
+    FlashCall f{batch, heads, heads / kv_heads, n_q, n_kv, head_dim, dtype == PLI_F16, causal != 0,
+                V7Strides{strides[0], strides[1], strides[2], strides[3], strides[4], strides[5],
+                          strides[6], strides[7], strides[8], strides[9], strides[10], strides[11]},
+                scale, 0};
+    f.mfma_operands = dtype != PLI_F32 && aligned16(q) && aligned16(k) && aligned16(v) && aligned16(o);
+    if (f.mfma_operands) f.cus = cu_count(s);
+    const FlashPlan plan = plan_flash(f, variant);
+    if (plan.family != FlashFamily::generic) return launch_mfma(f, plan, q, k, v, o, s);
     if (head_dim > GDMAX) {
         set_error("pli_flash_attn_fwd: head_dim %d > %d unsupported on the generic path", head_dim,
                   GDMAX);
         return PLI_EUNSUPPORTED;
     }
-    switch (dtype) {
-        case PLI_F32:
-            return launch_generic<float>(q, k, v, o, batch, heads, group, n_q, n_kv, head_dim, st, scale, causal, s);
-        case PLI_F16:
-            return launch_generic<f16_t>(q, k, v, o, batch, heads, group, n_q, n_kv, head_dim, st, scale, causal, s);
-        default:
-            return launch_generic<bf16_t>(q, k, v, o, batch, heads, group, n_q, n_kv, head_dim, st, scale, causal, s);
-    }
+    if (dtype == PLI_F32) return launch_generic<float>(f, q, k, v, o, s);
+    return f.fp16 ? launch_generic<f16_t>(f, q, k, v, o, s) : launch_generic<bf16_t>(f, q, k, v, o, s);
 }
 
 extern "C" int pli_flash_attn_fwd(const void* q, const void* k, const void* v, void* o,

@@ -8,8 +8,8 @@
 // wave's VALU stream runs under the other's MFMAs.  The body is one generated
 // instruction stream (flash_pp64_asm.h from tools/v14/pp64.py, which also
 // holds the register plan and the wait-count reasoning); the numerics are
-// attn_fwd_v13's (bf16: the l >= 1 check; fp16: the P-bit check, no QSCALE).  The arguments are launch_attn_v13's (flash_v13.hip)
-// with 512-row blocks; one block per workgroup.
+// attn_fwd_v13's (bf16: the l >= 1 check; fp16: the P-bit check, no QSCALE).  The arguments are pack_v13's (flash_plan.h)
+// with 512-row blocks.
 #include "flash_v13.h"
 #ifdef PLI_PP64_AB_HEADER  // timing A/B builds (tools/v14/build_pp64_ab.sh)
 #include PLI_PP64_AB_HEADER
@@ -33,7 +33,7 @@ namespace {
 
 PLI_PP64_KERNEL(attn_fwd_pp64, PLI_PP64_BODY)
 // fp16: P packed to fp16 and checked by the bit-14 test at the end of each
-// vector phase (v13's fp16 rule), the mu offset from the launcher's
+// vector phase (v13's fp16 rule), the mu offset from the planner's
 // v13_muoff_f16
 PLI_PP64_KERNEL(attn_fwd_pp64h, PLI_PP64H_BODY)
 // causal (bottom-right, Nq and Nk - Nq multiples of 64): per wave, the
@@ -44,21 +44,11 @@ PLI_PP64_KERNEL(attn_fwd_pp64hc, PLI_PP64HC_BODY)
 
 }  // namespace
 
-int launch_pp64(bool fp16, bool causal, unsigned grid, const V13Args& a, hipStream_t stream) {
-    if (causal) {
-        if (fp16) {
-            hipLaunchKernelGGL(attn_fwd_pp64hc, dim3(grid), dim3(512), 0, stream, a);
-            return launch_status("attn_fwd_pp64hc");
-        }
-        hipLaunchKernelGGL(attn_fwd_pp64c, dim3(grid), dim3(512), 0, stream, a);
-        return launch_status("attn_fwd_pp64c");
-    }
-    if (fp16) {
-        hipLaunchKernelGGL(attn_fwd_pp64h, dim3(grid), dim3(512), 0, stream, a);
-        return launch_status("attn_fwd_pp64h");
-    }
-    hipLaunchKernelGGL(attn_fwd_pp64, dim3(grid), dim3(512), 0, stream, a);
-    return launch_status("attn_fwd_pp64");
+V13Entry pp64_entry(bool fp16, bool causal, bool ragged) {
+    static const V13Entry table[2][2] = {  // [causal][fp16]
+        {PLI_V13_ENTRY(attn_fwd_pp64), PLI_V13_ENTRY(attn_fwd_pp64h)},
+        {PLI_V13_ENTRY(attn_fwd_pp64c), PLI_V13_ENTRY(attn_fwd_pp64hc)}};
+    return ragged ? V13Entry{nullptr, nullptr} : table[causal][fp16];
 }
 
 }  // namespace pli

@@ -1012,13 +1012,12 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_v12(
 
 }  // namespace
 
-bool attn_v12_ok(int D, int is_bf16, int causal, int Nk) {
-    return D == 128 && is_bf16 && !causal && Nk >= 64 && Nk % 64 == 0;
-}
-
-int launch_attn_v12(const void* q, const void* k, const void* v, void* o, int B, int H, int group, int Nq,
-                    int Nk, const V7Strides& st, float scale, hipStream_t stream, bool persistent, float thr,
-                    bool causal) {
+int launch_attn_v12(const FlashCall& f, const FlashPlan& plan, const void* q, const void* k, const void* v,
+                    void* o, hipStream_t stream) {
+    const int B = f.B, H = f.H, group = f.group, Nq = f.Nq, Nk = f.Nk;
+    const V7Strides& st = f.st;
+    const float scale = f.scale, thr = plan.thr;
+    const bool persistent = plan.persistent, causal = f.causal;
     PLI_REQUIRE(thr == 0.f || thr == 64.f, "attn_fwd_v12: defer-max threshold %g not built", thr);
     PLI_REQUIRE(!causal || (thr == 64.f && Nq <= Nk), "attn_fwd_v12: causal needs Nq <= Nk (THR 64)");
     const int qblocks = cdiv(Nq, 256);
@@ -1032,7 +1031,7 @@ int launch_attn_v12(const void* q, const void* k, const void* v, void* o, int B,
     // (else one block per workgroup, heaviest first).
     int grid = (int)nb;
     if (persistent && Nk >= 128) {
-        const int g = cu_count(stream) / 8 * 8;
+        const int g = f.cus / 8 * 8;
         if (g >= 8 && nb > g) grid = g;
         if (causal && grid < nb) {
             const int64_t bh = nb / qblocks, w = g / 8;

@@ -1,26 +1,26 @@
-// attn_fwd_v13's kernel argument block, shared by the D = 128 bodies
-// (flash_v13.hip) and the D = 64 ones (flash_v13_d64.hip): 64 dwords in the
-// layout of tools/v13/kernel.py ARG_LAYOUT (the generated body reads it
-// through the kernarg pointer).
+// The generated v13 / pp64 bodies as launch_attn_v13 (flash_v13.hip) sees
+// them: each file maps (fp16, causal, ragged -- Nk % 64 != 0) to one kernel
+// over the shared argument block V13Args (flash_plan.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <cstdint>
+#include "flash_plan.h"
 
 namespace pli {
 
-struct V13Args {
-    uint32_t w[64];
+struct V13Entry {
+    void (*kernel)(V13Args);
+    const char* route;  // the kernel's name, as pli_last_route reports it
 };
-static_assert(sizeof(V13Args) == 256, "V13Args layout");
+#define PLI_V13_ENTRY(kernel) V13Entry{kernel, #kernel}
 
-// launch one of the head-dim-64 bodies (bf16 / fp16, plain / causal /
-// ragged -- Nk % 64 != 0, non-causal) on `grid` workgroups of 256 threads;
-// returns the launch status
-int launch_v13_d64(bool fp16, bool causal, bool ragged, unsigned grid, const V13Args& a, hipStream_t stream);
-// attn_fwd_pp64 / pp64h / pp64c / pp64hc (flash_pp64.hip): head dim 64, bf16 /
-// fp16, Nk % 64 == 0 (causal: Nq and Nk - Nq too), the arguments with
-// 512-row blocks, workgroups of 512 threads
-int launch_pp64(bool fp16, bool causal, unsigned grid, const V13Args& a, hipStream_t stream);
+V13Entry v13_d128_entry(bool fp16, bool causal, bool ragged);  // flash_v13.hip: workgroups of 256 threads
+V13Entry v13_d64_entry(bool fp16, bool causal, bool ragged);   // flash_v13_d64.hip: 256 threads
+// flash_pp64.hip: head dim 64, Nk % 64 == 0 (never ragged; causal: Nq and
+// Nk - Nq too), the arguments with 512-row blocks, workgroups of 512 threads
+V13Entry pp64_entry(bool fp16, bool causal, bool ragged);
+
+// launch `entry` on `grid` workgroups of `block` threads; returns the launch status
+int launch_v13_body(const V13Entry& entry, unsigned grid, unsigned block, const V13Args& args, hipStream_t stream);
 
 }  // namespace pli

@@ -4,7 +4,7 @@
 // first halves of the D = 128 ones (same swizzle, fragment offsets and DMA
 // piece map), 4 LDS-DMA pieces per wave and 32 + 32 MFMAs per 64 x 64
 // wave-tile.  bf16 and fp16, plain, causal and ragged (Nk % 64 != 0); flash_v13.hip's launcher
-// fills the arguments and calls launch_v13_d64.
+// packs the arguments (pack_v13) and launches the body v13_d64_entry names.
 #include "flash_v13.h"
 #ifdef PLI_V13D64_AB_HEADER  // timing-only A/B builds (tools/build_v13_ab.sh)
 #include PLI_V13D64_AB_HEADER
@@ -38,37 +38,13 @@ PLI_V13_D64_KERNEL(attn_fwd_v13hrc_d64, PLI_V13HRC_D64_BODY)
 
 }  // namespace
 
-int launch_v13_d64(bool fp16, bool causal, bool ragged, unsigned grid, const V13Args& a, hipStream_t stream) {
-    if (ragged && causal) {
-        if (fp16) {
-            hipLaunchKernelGGL(attn_fwd_v13hrc_d64, dim3(grid), dim3(256), 0, stream, a);
-            return launch_status("attn_fwd_v13hrc_d64");
-        }
-        hipLaunchKernelGGL(attn_fwd_v13rc_d64, dim3(grid), dim3(256), 0, stream, a);
-        return launch_status("attn_fwd_v13rc_d64");
-    }
-    if (ragged) {
-        if (fp16) {
-            hipLaunchKernelGGL(attn_fwd_v13hr_d64, dim3(grid), dim3(256), 0, stream, a);
-            return launch_status("attn_fwd_v13hr_d64");
-        }
-        hipLaunchKernelGGL(attn_fwd_v13r_d64, dim3(grid), dim3(256), 0, stream, a);
-        return launch_status("attn_fwd_v13r_d64");
-    }
-    if (fp16 && causal) {
-        hipLaunchKernelGGL(attn_fwd_v13hc_d64, dim3(grid), dim3(256), 0, stream, a);
-        return launch_status("attn_fwd_v13hc_d64");
-    }
-    if (fp16) {
-        hipLaunchKernelGGL(attn_fwd_v13h_d64, dim3(grid), dim3(256), 0, stream, a);
-        return launch_status("attn_fwd_v13h_d64");
-    }
-    if (causal) {
-        hipLaunchKernelGGL(attn_fwd_v13c_d64, dim3(grid), dim3(256), 0, stream, a);
-        return launch_status("attn_fwd_v13c_d64");
-    }
-    hipLaunchKernelGGL(attn_fwd_v13_d64, dim3(grid), dim3(256), 0, stream, a);
-    return launch_status("attn_fwd_v13_d64");
+V13Entry v13_d64_entry(bool fp16, bool causal, bool ragged) {
+    static const V13Entry table[2][2][2] = {  // [ragged][causal][fp16]
+        {{PLI_V13_ENTRY(attn_fwd_v13_d64), PLI_V13_ENTRY(attn_fwd_v13h_d64)},
+         {PLI_V13_ENTRY(attn_fwd_v13c_d64), PLI_V13_ENTRY(attn_fwd_v13hc_d64)}},
+        {{PLI_V13_ENTRY(attn_fwd_v13r_d64), PLI_V13_ENTRY(attn_fwd_v13hr_d64)},
+         {PLI_V13_ENTRY(attn_fwd_v13rc_d64), PLI_V13_ENTRY(attn_fwd_v13hrc_d64)}}};
+    return table[ragged][causal][fp16];
 }
 
 }  // namespace pli

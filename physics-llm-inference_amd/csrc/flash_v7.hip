@@ -841,15 +841,15 @@ int launch_v7_typed(const void* q, const void* k, const void* v, void* o, int B,
 
 }  // namespace
 
-int launch_attn_v7(const void* q, const void* k, const void* v, void* o, int B, int H, int group,
-                   int Nq, int Nk, int D, const V7Strides& st, float scale, int causal, int is_bf16,
-                   hipStream_t stream, int sub) {
-    const float c = scale * 1.4426950408889634f;  // log2(e) folded into the Q prescale
-    if (is_bf16)
-        return D == 128 ? launch_v7_typed<bf16_t, 128>(q, k, v, o, B, H, group, Nq, Nk, st, c, causal, stream, sub)
-                        : launch_v7_typed<bf16_t, 64>(q, k, v, o, B, H, group, Nq, Nk, st, c, causal, stream, sub);
-    return D == 128 ? launch_v7_typed<f16_t, 128>(q, k, v, o, B, H, group, Nq, Nk, st, c, causal, stream, sub)
-                    : launch_v7_typed<f16_t, 64>(q, k, v, o, B, H, group, Nq, Nk, st, c, causal, stream, sub);
+int launch_attn_v7(const FlashCall& f, const FlashPlan& plan, const void* q, const void* k, const void* v,
+                   void* o, hipStream_t stream) {
+    const float c = f.scale * 1.4426950408889634f;  // log2(e) folded into the Q prescale
+    const int B = f.B, H = f.H, group = f.group, Nq = f.Nq, Nk = f.Nk, causal = f.causal, sub = plan.sub;
+    if (!f.fp16)
+        return f.D == 128 ? launch_v7_typed<bf16_t, 128>(q, k, v, o, B, H, group, Nq, Nk, f.st, c, causal, stream, sub)
+                          : launch_v7_typed<bf16_t, 64>(q, k, v, o, B, H, group, Nq, Nk, f.st, c, causal, stream, sub);
+    return f.D == 128 ? launch_v7_typed<f16_t, 128>(q, k, v, o, B, H, group, Nq, Nk, f.st, c, causal, stream, sub)
+                      : launch_v7_typed<f16_t, 64>(q, k, v, o, B, H, group, Nq, Nk, f.st, c, causal, stream, sub);
 }
 
 }  // namespace pli

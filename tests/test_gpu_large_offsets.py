@@ -1,7 +1,7 @@
 """Operands whose byte extents cross 2^31 / 2^32 (huge strides, small compute):
 the kernels address a head's rows / a tile's rows by 32-bit per-lane offsets
 from a 64-bit base, and each fast route states the extent it takes
-(flash_v13.hip attn_v13_ok: a Q / O head's rows below 2^32 bytes; gemm_w5.hip:
+(flash_plan.h attn_v13_ok: a Q / O head's rows below 2^32 bytes; gemm_w5.hip:
 256 rows of A / B below 2^31 bytes); past that the dispatch must fall back to a
 kernel that is still correct.  Every case runs once just inside and once just
 outside such a bound and is checked against fp32 torch math on contiguous
@@ -173,7 +173,7 @@ def test_flash_long_sequences(shape, dtype, causal):
 
 
 # a chunk of new rows over a cache-long key stream: the causal walk packs the
-# key-tile count into 16 bits (flash_v13.hip attn_v13_ok: cdiv(Nk, 64) <=
+# key-tile count into 16 bits (flash_plan.h attn_v13_ok: cdiv(Nk, 64) <=
 # 0xFFFF), so 65535 tiles run v13 and one tile more the fallback
 @pytest.mark.parametrize("causal", (False, True))
 @pytest.mark.parametrize("nk", (65535 * 64, 65535 * 64 + 64, 65535 * 64 - 13))

@@ -1,60 +1,61 @@
 """Which kernel each call runs (pli_last_route): the dispatch tables that
 DESIGN.md §0 / §3 and include/pli.h state, checked on the device.  Flash:
-csrc/flash_attn.hip launch_mfma -> attn_v13_ok (flash_v13.hip) -> v12
-(attn_v12_ok) -> v7 / v10 -> the generic kernel; each routed call is also
-checked against fp32 torch attention, so a route is only "taken" when its
-result is right."""
+csrc/flash_plan.h plan_flash -- pp64 (attn_pp64_ok, where its blocks fill the
+chip) -> v13 (attn_v13_ok) -> v12 (attn_v12_ok) -> v7 / v10 -> v2, the generic
+kernel for what no MFMA kernel reads; the same cases are asked of the planner
+on the CPU in tests/test_flash_plan.py.  Each routed call is also checked
+against fp32 torch attention, so a route is only "taken" when its result is
+right."""
 from __future__ import annotations
 
 import pytest
 import torch
 
+from flash_route_cases import BF, FLASH, FORCED, forced_id
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
 
-def v13(dtype, D, causal, ragged):
-    return ("attn_fwd_v13" + ("h" if dtype == torch.float16 else "") +
-            ("rc" if ragged and causal else "r" if ragged else "c" if causal else "") + ("_d64" if D == 64 else ""))
-
-
-BF, FP = torch.bfloat16, torch.float16
-# (B, H, Hkv, Nq, Nk, D, dtype, causal, expected route)
-FLASH = [
-    *[(2, 4, 2, 256, 256, D, dt, c, v13(dt, D, c, False)) for D in (128, 64) for dt in (BF, FP) for c in (False, True)],
-    *[(2, 4, 2, 200, 200, D, dt, c, v13(dt, D, c, True)) for D in (128, 64) for dt in (BF, FP) for c in (False, True)],
-    (1, 8, 8, 128, 1024, 128, BF, True, "attn_fwd_v13c"),      # chunked prefill, offset 896
-    (1, 8, 8, 100, 1000, 128, BF, True, "attn_fwd_v13rc"),     # offset 900, ragged
-    (1, 8, 2, 1, 777, 64, FP, True, "attn_fwd_v13hrc_d64"),    # one query row
-    (2, 4, 4, 64, 64, 128, BF, False, "attn_fwd_v12"),          # Nk = 64: v12
-    (2, 4, 4, 64, 64, 128, BF, True, "attn_fwd_v12"),
-    (2, 4, 4, 64, 64, 128, FP, False, "attn_fwd_v7"),           # v12 is bf16 only
-    (2, 4, 4, 40, 40, 128, BF, False, "attn_fwd_v7"),           # Nk < 64
-    (2, 4, 4, 300, 200, 128, BF, True, "attn_fwd_v7"),          # causal Nq > Nk
-    (2, 4, 4, 128, 256, 96, BF, False, "attn_fwd_generic"),     # head dim 96
-    (2, 4, 4, 128, 256, 128, torch.float32, False, "attn_fwd_generic"),
-    (2, 4, 4, 128, 0, 128, BF, False, "attn_fwd_generic"),      # no keys: O = 0
-]
-
-
-@pytest.mark.parametrize("case", FLASH, ids=lambda c: "b{}h{}kv{}q{}k{}d{}-{}-causal{}".format(
-    *c[:6], str(c[6]).split(".")[-1], int(c[7])))
-def test_flash_route(case):
+def flash_case(B, H, Hkv, Nq, Nk, D, dt, causal, want, variant=None, scale=None):
+    """one call through the public ABI: its route, and its result against fp32 torch attention"""
     import pli_hip
-    B, H, Hkv, Nq, Nk, D, dt, causal, want = case
     g = torch.Generator(device=DEV).manual_seed(Nq + Nk + D)
-    q = torch.randn(B, H, Nq, D, device=DEV, generator=g).to(dt)
+    # an explicit scale > 0: Q shrunk so the scaled scores spread as at the default D^-1/2 -- a softmax
+    # near one-hot would return single V values up to ~4.5, whose 16-bit rounding alone (2^-6) passes 1e-2
+    amp = D ** -0.5 / scale if scale is not None and scale > 0 else 1.0
+    q = (torch.randn(B, H, Nq, D, device=DEV, generator=g) * amp).to(dt)
     k = torch.randn(B, Hkv, Nk, D, device=DEV, generator=g).to(dt)
     v = torch.randn(B, Hkv, Nk, D, device=DEV, generator=g).to(dt)
-    out = pli_hip.flash_attn_fwd(q, k, v, causal=causal)
+    out = pli_hip.flash_attn_fwd(q, k, v, scale=scale, causal=causal, variant=variant)
     assert pli_hip.last_route() == want
     G = H // Hkv
-    s = (q.float() @ k.float().repeat_interleave(G, 1).transpose(-1, -2)) * D ** -0.5
+    s = (q.float() @ k.float().repeat_interleave(G, 1).transpose(-1, -2)) * (D ** -0.5 if scale is None else scale)
     if causal:
         s = s.masked_fill(torch.ones(Nq, Nk, dtype=torch.bool, device=DEV).triu(Nk - Nq + 1), float("-inf"))
     ref = torch.softmax(s, -1) @ v.float().repeat_interleave(G, 1) if Nk else torch.zeros_like(q, dtype=torch.float32)
     ref = torch.nan_to_num(ref)  # (causal Nq > Nk: rows with no key are 0 here and NaN in torch)
     assert (out.float() - ref).abs().max().item() <= 1e-2
+
+
+@pytest.mark.parametrize("case", FLASH, ids=lambda c: "b{}h{}kv{}q{}k{}d{}-{}-causal{}".format(
+    *c[:6], str(c[6]).split(".")[-1], int(c[7])))
+def test_flash_route(case):
+    flash_case(*case)
+
+
+@pytest.mark.parametrize("case", FORCED, ids=forced_id)
+def test_flash_forced_variant(case):
+    """every variant number where it applies and where it falls through, c > 1 and scale <= 0"""
+    variant, *shape, scale, want = case
+    flash_case(*shape, want, variant=variant, scale=scale)
+
+
+@pytest.mark.parametrize("short", (0, 1), ids=("fills", "one-short"))
+def test_flash_fill_rule(short):
+    """the default at D 64 non-causal: pp64 where B H ceil(Nq / 512) blocks fill the CUs, else v13"""
+    H = torch.cuda.get_device_properties(0).multi_processor_count - short
+    flash_case(1, H, H, 64, 128, 64, BF, False, "attn_fwd_v13_d64" if short else "attn_fwd_pp64")
 
 
 def test_gemm_and_decode_routes():

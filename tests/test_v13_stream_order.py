@@ -41,7 +41,7 @@ def stream(B, H, Hkv, Nq, Nk, grid):
 
 
 def expected(B, H, Hkv, Nq, Nk, G):
-    Nqv = Nq + ((Nk - Nq) & 63)  # virtual rows (launch_attn_v13): the diagonal on tile boundaries
+    Nqv = Nq + ((Nk - Nq) & 63)  # virtual rows (pack_v13): the diagonal on tile boundaries
     QB, nt, offt = -(-Nqv // 256), -(-Nk // 64), (Nk - Nqv) // 64
     row = lambda t: Nk - 64 if t == nt - 1 else 64 * t  # noqa: E731  (ragged Nk: the last tile shifted back)
     nb = B * H * QB

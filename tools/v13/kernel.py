@@ -203,7 +203,7 @@ SGPR_LAST = 99
 SGPR_SKIP = (32,)
 M0SAVE = (V(217), 63)  # m0 is saved in lane 63 of v217 (the stamp build's record: lanes 0-8) and restored at exit
 
-# kernel argument dwords (V13Args in csrc/flash_v13.hip)
+# kernel argument dwords (V13Args in csrc/flash_plan.h)
 # (dwords 0..36 are reloaded into s56..s92 at every block transition -- no
 # instruction writes them, and dropping the reload was measured level; 37..
 # are read at init or by a single s_load where needed).  "shifts" packs the

@@ -1,5 +1,6 @@
-"""Host-side argument block of attn_fwd_v13 (the Python mirror of
-launch_attn_v13 in csrc/flash_v13.hip) and an emulator driver."""
+"""Host-side argument block of attn_fwd_v13 and an emulator driver.  args_for /
+pair_walk are the Python twin of pack_v13 (csrc/flash_plan.h), the block the
+GPU gets; tests/test_flash_plan.py compares the two word for word."""
 from __future__ import annotations
 
 import math
@@ -25,7 +26,7 @@ def magic(d: int):
 
 def pair_walk(nb, qblocks, G):
     """(walk, lgG8, lghq, per, hx): the causal pair walk where it tiles the
-    grid exactly (launch_attn_v13's rule), else the remap walk"""
+    grid exactly (pack_v13's rule), else the remap walk"""
     bh = nb // qblocks
     w = G // 8
     hq = qblocks // 2
@@ -41,7 +42,7 @@ def args_for(qa, ka, va, oa, B, H, Hkv, Nq, Nk, strides_el, scale, G, muoff=7.0,
     (qb, qh, qn, kb, kh, kn, vb, vh, vn, ob, oh, on) of bf16 tensors"""
     st = [2 * s for s in strides_el]
     # causal: rows are virtual, shifted by s = (-Nq) & 63 so the diagonal sits
-    # on 64-key tile boundaries (launch_attn_v13)
+    # on 64-key tile boundaries (pack_v13)
     Nqv = Nq + ((Nk - Nq) & 63) if causal else Nq
     qblocks = -(-Nqv // 256)
     nblocks = B * H * qblocks

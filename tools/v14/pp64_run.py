@@ -1,5 +1,5 @@
 """Emulator driver for attn_fwd_pp64 (tools/v14/pp64.py): the argument block
-of launch_attn_v13 with 512-row blocks (csrc/flash_v13.hip, pp64 route) and
+of pack_v13 with 512-row blocks (csrc/flash_plan.h, a pp64 plan) and
 one workgroup of 8 waves per block."""
 from __future__ import annotations
 
@@ -25,6 +25,21 @@ def program(dtype="bf16", causal=False):
         prog = PP64(tag="emu", dtype=dtype, causal=causal).build(in_kernarg=S(0, 2), in_wg=S(2), in_wave=S(3))
         _PROG[key], _ = finalize(prog)
     return _PROG[key]
+
+
+def args_for(qa, ka, va, oa, B, H, Hkv, Nq, Nk, strides_el, scale, G, muoff=62.0, causal=False):
+    """v13's argument block (R.args_for) with pp64's 512-row blocks: the
+    Python twin of pack_v13 (csrc/flash_plan.h) for a pp64 plan"""
+    from v13.kernel import AI
+    qblocks = -(-Nq // 512)
+    args = R.args_for(qa, ka, va, oa, B, H, Hkv, Nq, Nk, strides_el, scale, G, muoff, False)
+    args[AI["qblocks"]], args[AI["nblocks"]] = qblocks, B * H * qblocks
+    args[AI["magq"]], shq = R.magic(qblocks)
+    args[AI["shifts"]] = (int(args[AI["shifts"]]) & ~31) | shq
+    if causal:  # bottom-right, Nq and Nk - Nq multiples of 64: the remap walk, heaviest first
+        assert Nq % 64 == 0 and (Nk - Nq) % 64 == 0 and Nk >= Nq
+        args[AI["cw"]], args[AI["offt"]] = 2, (Nk - Nq) // 64
+    return args
 
 
 def run(q, k, v, scale=None, muoff=62.0, layout="bhsd", dtype="bf16", grid=None, causal=False):
@@ -56,15 +71,9 @@ def run(q, k, v, scale=None, muoff=62.0, layout="bhsd", dtype="bf16", grid=None,
     qblocks = -(-Nq // 512)
     nb = B * H * qblocks
     G = nb if grid is None else grid  # grid < nb: the persistent walk (L, L + G, ...)
-    args = R.args_for(qa, ka, va, oa, B, H, Hkv, Nq, Nk, list(sq) + list(sk) + list(sv) + list(so), scale, G,
-                      muoff, False)
-    from v13.kernel import AI
-    args[AI["qblocks"]], args[AI["nblocks"]] = qblocks, nb
-    args[AI["magq"]], shq = R.magic(qblocks)
-    args[AI["shifts"]] = (int(args[AI["shifts"]]) & ~31) | shq
-    if causal:  # bottom-right, Nq and Nk - Nq multiples of 64: the remap walk, heaviest first
-        assert Nq % 64 == 0 and (Nk - Nq) % 64 == 0 and Nk >= Nq and grid is None
-        args[AI["cw"]], args[AI["offt"]] = 2, (Nk - Nq) // 64
+    assert not causal or grid is None  # causal: one block per workgroup
+    args = args_for(qa, ka, va, oa, B, H, Hkv, Nq, Nk, list(sq) + list(sk) + list(sv) + list(so), scale, G, muoff,
+                    causal)
     kaddr = heap.alloc(args.nbytes, args.tobytes())
     em = E.Emu(program(dtype, causal), heap)
     for wg in range(G):
