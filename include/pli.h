@@ -350,6 +350,69 @@ int pli_attn_decode_dev(const void* q, const void* k, const void* v, void* o,
                         int n_kv_add, void* workspace, size_t workspace_bytes,
                         int dtype, void* stream);
 
+/* Paged KV cache: decode attention straight over the block pool, and the
+ * append that feeds it.  Serves ch07/paged_memory.py:16-51,171-175: the
+ * reference's PagedKVCache allocates the pools k_cache / v_cache
+ * [num_blocks, num_layers, block_size, num_heads, head_dim] and describes, but
+ * never writes, the attention kernel that "reads from scattered blocks / uses
+ * block table for indirection".
+ *
+ * block_table: device int32 [batch, max_blocks_per_seq], entry (b, i) the
+ *   page that holds tokens i*block_size .. (i+1)*block_size - 1 of sequence b.
+ *   Entries are clamped into [0, num_blocks - 1] before use, so a stale entry
+ *   reads the wrong page, never memory outside the pool; unused entries should
+ *   still hold a valid page index.
+ * seq_lens: device int32 [batch].  Both are read on the device, nothing is
+ *   allocated or synchronised: the calls can be captured in a graph and
+ *   replayed while the table and the lengths change in place.
+ * Pools: k_pool / v_pool point at page 0; a layer view k_cache[:, layer] of
+ *   the reference layout is passed without a copy through its strides.
+ *
+ * pli_attn_decode_paged: sequence b attends over its first
+ *   n_kv(b) = clamp(seq_lens[b] + n_kv_add, 0, max_kv) tokens.  q / o are
+ *   [B, Hq, n_q, D]-indexed.  strides[12] in elements: {q_b, q_h, q_n,
+ *   k_page, k_token, k_head, v_page, v_token, v_head, o_b, o_h, o_n}.
+ *   max_kv is a host upper bound on every length (<= max_blocks_per_seq *
+ *   block_size): the split-K grid and the workspace are sized for it, as
+ *   pli_attn_decode_dev's are for n_kv_max.  causal masks bottom-right per
+ *   sequence (query i sees keys j <= n_kv(b) - n_q + i); a row that sees no
+ *   key (an empty sequence among them) is written as 0.
+ *   The MFMA kernel attn_decode_paged takes bf16/fp16, D in {64, 128},
+ *   n_q * Hq/Hkv <= 16 rows per kv head, a power-of-two block_size >= 16,
+ *   scale > 0, strides % 8 == 0 and 16-byte aligned operands; everything else
+ *   (fp32, head_dim <= 256, any block_size) runs attn_decode_paged_generic,
+ *   a correctness path.  `workspace` (16-byte aligned, fp32 partials) must
+ *   hold pli_attn_decode_paged_workspace_size bytes; NULL when that is 0.
+ *   pli_last_route: "attn_decode_paged", "attn_decode_paged+
+ *   attn_decode_paged_combine" or "attn_decode_paged_generic".
+ * pli_kv_append_paged: token t of k_new / v_new ([B, n_new, Hkv, D]) of
+ *   sequence b goes to logical position seq_lens[b] + t; positions >=
+ *   max_blocks_per_seq * block_size are dropped.  seq_lens is not advanced
+ *   (the caller adds n_new on the device).  strides[12] in elements: {kn_b,
+ *   kn_h, kn_n, k_page, k_token, k_head, v_page, v_token, v_head, vn_b, vn_h,
+ *   vn_n}.  Rows of whole 16-byte chunks: head_dim and every stride a multiple
+ *   of 8 (bf16/fp16) or 4 (fp32) elements, 16-byte aligned operands.
+ * PLI_EINVAL before any HIP call for bad shapes, heads % kv_heads != 0, null
+ * pointers, a non-finite scale, block_size <= 0, max_kv > max_blocks_per_seq *
+ * block_size, a short workspace; an empty output (batch == 0, n_q == 0,
+ * n_new == 0) returns PLI_OK and its operands may be NULL. */
+size_t pli_attn_decode_paged_workspace_size(int batch, int heads, int kv_heads,
+                                            int n_q, int max_kv, int head_dim);
+int pli_attn_decode_paged(const void* q, const void* k_pool, const void* v_pool,
+                          void* o, const int32_t* block_table,
+                          const int32_t* seq_lens, int batch, int heads,
+                          int kv_heads, int n_q, int head_dim, int block_size,
+                          int num_blocks, int max_blocks_per_seq, int max_kv,
+                          const int64_t* strides, float scale, int causal,
+                          int n_kv_add, void* workspace, size_t workspace_bytes,
+                          int dtype, void* stream);
+int pli_kv_append_paged(const void* k_new, const void* v_new, void* k_pool,
+                        void* v_pool, const int32_t* block_table,
+                        const int32_t* seq_lens, int batch, int n_new,
+                        int kv_heads, int head_dim, int block_size,
+                        int num_blocks, int max_blocks_per_seq,
+                        const int64_t* strides, int dtype, void* stream);
+
 /* ------------------------------------------------------------------------
  * Tuning section: the same operations with an explicit kernel choice, for
  * A/B runs (tools/tune.py) and the per-variant parity tests.  Not part of

@@ -1,0 +1,202 @@
+"""Paged KV cache -- mirror of ``ch07/paged_memory.py``.
+
+The allocator half keeps the reference's interface: ``BlockTable`` and
+``PagedKVCache`` with the pools ``k_cache`` / ``v_cache`` laid out
+[num_blocks, num_layers, block_size, num_heads, head_dim]
+(``ch07/paged_memory.py:16-51``), a free set, one block table per request,
+``allocate_blocks`` / ``extend_blocks`` / ``free_blocks_for_request`` and the
+``get_memory_usage`` report (``:53-137``).
+
+The reference stops at the bookkeeping: its text describes an attention
+kernel that "reads from scattered blocks / uses block table for indirection"
+(``:171-175``) and never writes one.  Here the pools can be written and
+attended over in place, through ``pli_kv_append_paged`` and
+``pli_attn_decode_paged`` (csrc/paged_attn.hip):
+
+* ``tables(request_ids)`` packs the requests' block tables and lengths into
+  device int32 tensors,
+* ``append(layer, k_new, v_new, block_table, seq_lens)`` stores the newest
+  tokens of every sequence,
+* ``attend(layer, q, block_table, seq_lens)`` runs decode attention over each
+  sequence's own pages and length.
+
+No page is gathered into a contiguous tensor on the way.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass, field
+
+import torch
+
+import pli_hip
+
+
+@dataclass
+class BlockTable:
+    request_id: int
+    block_indices: list[int] = field(default_factory=list)
+    num_tokens: int = 0
+
+    def num_blocks(self) -> int:
+        return len(self.block_indices)
+
+
+class PagedKVCache:
+    def __init__(self, num_blocks: int, block_size: int, num_layers: int, num_heads: int, head_dim: int,
+                 dtype: torch.dtype = torch.float16, device: str = "cuda"):
+        self.num_blocks = num_blocks
+        self.block_size = block_size
+        self.num_layers = num_layers
+        self.num_heads = num_heads
+        self.head_dim = head_dim
+        self.dtype = dtype
+        self.device = device
+
+        self.free_blocks: set[int] = set(range(num_blocks))
+        self.block_tables: dict[int, BlockTable] = {}
+
+        # the pools exist only on a device (None otherwise, as in the reference)
+        self.k_cache = self.v_cache = None
+        if torch.cuda.is_available() and torch.device(device).type == "cuda":
+            shape = (num_blocks, num_layers, block_size, num_heads, head_dim)
+            self.k_cache = torch.zeros(shape, dtype=dtype, device=device)
+            self.v_cache = torch.zeros(shape, dtype=dtype, device=device)
+
+    # ------------------------------------------------------------ allocator --
+    def _blocks_for(self, num_tokens: int) -> int:
+        return -(-num_tokens // self.block_size)
+
+    def _take(self, count: int, what: str) -> list[int]:
+        if count > len(self.free_blocks):
+            raise RuntimeError(f"Not enough free blocks{what}: need {count}, have {len(self.free_blocks)}")
+        return [self.free_blocks.pop() for _ in range(count)]
+
+    def allocate_blocks(self, request_id: int, num_tokens: int) -> BlockTable:
+        pages = self._take(self._blocks_for(num_tokens), "")
+        table = BlockTable(request_id=request_id, block_indices=pages, num_tokens=num_tokens)
+        self.block_tables[request_id] = table
+        return table
+
+    def extend_blocks(self, request_id: int, new_tokens: int) -> None:
+        if request_id not in self.block_tables:
+            raise KeyError(f"Request {request_id} not found")
+        table = self.block_tables[request_id]
+        total = table.num_tokens + new_tokens
+        # a page is taken only when the new tokens cross a block boundary
+        grow = self._blocks_for(total) - self._blocks_for(table.num_tokens)
+        table.block_indices.extend(self._take(grow, " for extension"))
+        table.num_tokens = total
+
+    def free_blocks_for_request(self, request_id: int) -> int:
+        table = self.block_tables.pop(request_id, None)
+        if table is None:
+            return 0
+        self.free_blocks.update(table.block_indices)
+        return len(table.block_indices)
+
+    def get_num_free_blocks(self) -> int:
+        return len(self.free_blocks)
+
+    def get_memory_usage(self) -> dict:
+        free = len(self.free_blocks)
+        used = self.num_blocks - free
+        # K and V, every layer, 2 bytes per element (the reference's fp16 figure)
+        bytes_per_block = 2 * self.num_layers * self.block_size * self.num_heads * self.head_dim * 2
+        mb = 1024 * 1024
+        return {
+            "total_blocks": self.num_blocks,
+            "used_blocks": used,
+            "free_blocks": free,
+            "block_size_tokens": self.block_size,
+            "bytes_per_block": bytes_per_block,
+            "total_mb": self.num_blocks * bytes_per_block / mb,
+            "used_mb": used * bytes_per_block / mb,
+            "utilization": used / self.num_blocks if self.num_blocks > 0 else 0,
+        }
+
+    # ---------------------------------------------------------- device half --
+    def _pools(self, layer: int):
+        if self.k_cache is None:
+            raise pli_hip.PliError("PagedKVCache has no device pools (created off-device)")
+        if not 0 <= layer < self.num_layers:
+            raise IndexError(f"layer {layer} outside [0, {self.num_layers})")
+        # [num_blocks, block_size, heads, head_dim] views: the layer is in the page stride
+        return self.k_cache[:, layer], self.v_cache[:, layer]
+
+    def tables(self, request_ids, max_blocks: int | None = None):
+        """(block_table int32 [B, max_blocks], seq_lens int32 [B]) of the given
+        requests on the cache's device, in the order given.  seq_lens holds each
+        request's ``num_tokens``.  Entries past a request's blocks repeat its last
+        page (page 0 for a request without blocks), so every entry is a valid page
+        index.  max_blocks: the table width, default the longest request's (at
+        least 1); a fixed width keeps the tensors' shapes stable across steps."""
+        rows = [self.block_tables[r] for r in request_ids]  # KeyError for an unknown request
+        width = max([1] + [t.num_blocks() for t in rows]) if max_blocks is None else int(max_blocks)
+        if any(t.num_blocks() > width for t in rows) or width < 1:
+            raise ValueError(f"max_blocks {width} is narrower than a request's block table")
+        host = torch.tensor([t.block_indices + [t.block_indices[-1] if t.block_indices else 0] *
+                             (width - t.num_blocks()) for t in rows], dtype=torch.int32).reshape(len(rows), width)
+        lens = torch.tensor([t.num_tokens for t in rows], dtype=torch.int32)
+        dev = self.device if self.k_cache is None else self.k_cache.device
+        return host.to(dev), lens.to(dev)
+
+    def append(self, layer: int, k_new: torch.Tensor, v_new: torch.Tensor, block_table: torch.Tensor,
+               seq_lens: torch.Tensor) -> None:
+        """Store k_new / v_new [B, T, heads, head_dim] as the LAST T tokens of
+        every sequence: token t of sequence b goes to position
+        seq_lens[b] - T + t.  The order of a step is therefore extend_blocks(rid,
+        T), tables(...), append, attend -- the lengths ``tables`` returns already
+        count the new tokens."""
+        k_pool, v_pool = self._pools(layer)
+        start = seq_lens - k_new.shape[1]
+        pli_hip.kv_append_paged(k_new, v_new, k_pool, v_pool, block_table, start)
+
+    def attend(self, layer: int, q: torch.Tensor, block_table: torch.Tensor, seq_lens: torch.Tensor,
+               n_kv_add: int = 0, causal: bool = True) -> torch.Tensor:
+        """Attention of q [B, Sq, Hq, head_dim] over each sequence's first
+        seq_lens[b] + n_kv_add tokens of this layer's pages, read in place;
+        causal masks bottom-right per sequence.  Returns [B, Sq, Hq, head_dim]."""
+        k_pool, v_pool = self._pools(layer)
+        return pli_hip.attn_decode_paged(q, k_pool, v_pool, block_table, seq_lens, causal=causal,
+                                         n_kv_add=n_kv_add)
+
+
+def explain_paged_memory() -> str:
+    return """
+Paged KV cache on MI355X
+
+Why pages: a contiguous cache reserves max_seq_len rows per request, so short
+requests strand memory that no other request can use.
+
+How it works here:
+  - The pool is cut into blocks of block_size tokens (16 is typical).
+  - A free set hands blocks out; a request's block table lists its blocks in
+    logical order; freeing a request returns them to the set.
+  - A prompt of N tokens takes ceil(N / block_size) blocks; decoding takes one
+    more block each time a boundary is crossed.  Nothing is copied or
+    pre-reserved, and equal-sized blocks do not fragment.
+
+Attention over pages:
+  - pli_attn_decode_paged reads K and V rows straight from the scattered
+    blocks: row j of sequence b lives in page table[b][j // block_size] at
+    slot j % block_size.
+  - The table entries a step needs are fetched two steps ahead, so the extra
+    indirection stays off the critical path; every sequence attends over its
+    own length, read on the device, so the step replays in a captured graph.
+"""
+
+
+if __name__ == "__main__":
+    print(explain_paged_memory())
+    cache = PagedKVCache(num_blocks=100, block_size=16, num_layers=32, num_heads=32, head_dim=128, device="cpu")
+    print("empty:", cache.get_memory_usage())
+    first = cache.allocate_blocks(request_id=1, num_tokens=50)
+    print(f"request 1, 50 tokens: blocks {first.block_indices}, {cache.get_num_free_blocks()} free")
+    second = cache.allocate_blocks(request_id=2, num_tokens=100)
+    print(f"request 2, 100 tokens: blocks {second.block_indices}, {cache.get_num_free_blocks()} free")
+    cache.extend_blocks(request_id=1, new_tokens=30)
+    print(f"request 1 grown to {cache.block_tables[1].num_tokens} tokens: blocks {cache.block_tables[1].block_indices}")
+    print(f"request 2 freed: {cache.free_blocks_for_request(request_id=2)} blocks back, "
+          f"{cache.get_num_free_blocks()} free")
+    for key, value in cache.get_memory_usage().items():
+        print(f"  {key}: {value:.2f}" if isinstance(value, float) else f"  {key}: {value}")

@@ -27,6 +27,7 @@
 // fp32 statistics; the row sum is taken over the rounded P that P.V uses.
 #include <cmath>
 
+#include "decode_plan.h"
 #include "pli_common.h"
 
 namespace pli {
@@ -36,10 +37,7 @@ struct DecStrides {
     int64_t qb, qh, qn, kb, kh, kn, vb, vh, vn, ob, oh, on;
 };
 
-constexpr int DEC_WAVES = 4;
-constexpr int DEC_STEP = 32;                        // keys per wave step
-constexpr int DEC_QUANT = DEC_WAVES * DEC_STEP;     // chunk granularity
-constexpr int DEC_MAXM = 16;                        // query rows per kv head
+// DEC_WAVES / DEC_STEP / DEC_QUANT / DEC_MAXM: decode_plan.h
 
 template <int D, bool KLDS> struct DecLayout {
     static constexpr int KS = 2 * D + 16;             // K row stride in LDS (bytes)
@@ -342,27 +340,7 @@ __global__ __launch_bounds__(256) void attn_decode_combine(
     }
 }
 
-// Chunking: enough workgroups to keep every CU's loads in flight (~4 per CU),
-// at least one 32-key step per wave; chunk is a multiple of 4 waves x 32 keys.
-struct DecPlan {
-    int chunk, splits;
-};
-constexpr int64_t kDefaultTargetWgs = 1024;
-// Short caches (<= kNoSplitKeys keys) with >= kNoSplitWgs (batch, kv head)
-// pairs take one chunk per pair: the combine launch (~4.7 us) costs more than
-// the serial key loop it saves (graph decode step, batch 32, 560-key cache:
-// 1.279 -> 1.246 ms/token); with few pairs the split stays (batch 1: 8
-// one-chunk workgroups ran 0.715 vs 0.681 ms/token).
-constexpr int kNoSplitKeys = 1024, kNoSplitWgs = 128;
-DecPlan plan_decode(int64_t bh, int n_kv, int64_t kTargetWgs = kDefaultTargetWgs) {
-    const int64_t max_splits = cdiv(n_kv, DEC_QUANT);
-    int64_t splits = bh >= kTargetWgs || (n_kv <= kNoSplitKeys && bh >= kNoSplitWgs)
-                         ? 1
-                         : cdiv(kTargetWgs, bh);
-    splits = splits < 1 ? 1 : (splits > max_splits ? max_splits : splits);
-    const int chunk = (int)(cdiv(cdiv(n_kv, splits), DEC_QUANT) * DEC_QUANT);
-    return {chunk, (int)cdiv(n_kv, chunk)};
-}
+// DecPlan / plan_decode (the split-K chunking): decode_plan.h
 
 bool decode_fast_path(int heads, int kv_heads, int n_q, int n_kv, int head_dim, int dtype,
                       const int64_t* strides) {

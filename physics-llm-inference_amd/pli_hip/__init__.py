@@ -77,6 +77,12 @@ _SIGS = {
                             ctypes.c_size_t, _c_int, _vp],
     "pli_attn_decode": [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
                         ctypes.POINTER(_c_i64), _c_f32, _c_int, _vp, ctypes.c_size_t, _c_int, _vp],
+    "pli_attn_decode_paged_workspace_size": [_c_int] * 6,
+    "pli_attn_decode_paged": [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int,
+                              _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_i64), _c_f32, _c_int,
+                              _c_int, _vp, ctypes.c_size_t, _c_int, _vp],
+    "pli_kv_append_paged": [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int,
+                            _c_int, _c_int, ctypes.POINTER(_c_i64), _c_int, _vp],
     # tuning entry points (include/pli.h tuning section): explicit kernel variant
     "pli_flash_attn_fwd_variant": [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int,
                                    _c_int, ctypes.POINTER(_c_i64), _c_f32, _c_int, _c_int, _vp,
@@ -342,6 +348,103 @@ def attn_decode_dev(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tenso
                                        _dtype_code(q), _stream(dev))
     _check(rc, "pli_attn_decode_dev")
     return out
+
+
+# ------------------------------------------------------ paged KV cache
+def attn_decode_paged_workspace_bytes(B: int, H: int, Hkv: int, Sq: int, max_kv: int, D: int) -> int:
+    """fp32 split-K workspace of attn_decode_paged for sequences of up to max_kv keys"""
+    return int(lib().pli_attn_decode_paged_workspace_size(B, H, Hkv, Sq, max_kv, D))
+
+
+def _check_paged(what: str, x: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor,
+                 block_table: torch.Tensor, seq_lens: torch.Tensor):
+    """shared checks of the paged calls: x is q or k_new [B, S, H, D], the pools
+    [num_blocks, block_size, Hkv, D] views (any page stride), block_table int32
+    [B, max_blocks], seq_lens int32 [B]; returns the device"""
+    dev = _require_gpu(x, k_pool, v_pool)
+    for name, t in (("block_table", block_table), ("seq_lens", seq_lens)):
+        if not t.is_cuda or t.device != dev or t.dtype != torch.int32 or not t.is_contiguous():
+            raise PliError(f"{what}: {name} must be a contiguous int32 tensor on {dev}")
+    if x.dim() != 4 or k_pool.dim() != 4 or tuple(v_pool.shape) != tuple(k_pool.shape):
+        raise PliError(f"{what} expects [B, S, H, D] tokens and [num_blocks, block_size, Hkv, D] pools, got "
+                       f"{tuple(x.shape)} k{tuple(k_pool.shape)} v{tuple(v_pool.shape)}")
+    B, D = x.shape[0], x.shape[3]
+    if k_pool.shape[3] != D or block_table.dim() != 2 or block_table.shape[0] != B or tuple(seq_lens.shape) != (B,):
+        raise PliError(f"{what}: shape mismatch tokens{tuple(x.shape)} pool{tuple(k_pool.shape)} "
+                       f"table{tuple(block_table.shape)} seq_lens{tuple(seq_lens.shape)}")
+    if any(t.stride(-1) != 1 for t in (x, k_pool, v_pool) if t.numel()):
+        raise PliError(f"{what}: a unit head_dim stride is required (the pools are used in place)")
+    return dev
+
+
+def attn_decode_paged(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor,
+                      block_table: torch.Tensor, seq_lens: torch.Tensor, *, scale: float | None = None,
+                      causal: bool = True, n_kv_add: int = 0, max_kv: int | None = None,
+                      out: torch.Tensor | None = None, workspace: torch.Tensor | None = None
+                      ) -> torch.Tensor:
+    """Decode attention straight over a paged pool (the PagedKVCache of
+    ch07/paged_memory.py:16-51): q [B, Sq, Hq, D]; k_pool / v_pool
+    [num_blocks, block_size, Hkv, D] views such as k_cache[:, layer], used in
+    place; block_table int32 [B, max_blocks] of page indices; sequence b
+    attends over its first clamp(seq_lens[b] + n_kv_add, 0, max_kv) tokens,
+    read on the device (graph-replayable).  max_kv: a host bound on every
+    length, default max_blocks * block_size.  causal masks bottom-right per
+    sequence.  Returns [B, Sq, Hq, D]; a row that sees no key is 0."""
+    dev = _check_paged("attn_decode_paged", q, k_pool, v_pool, block_table, seq_lens)
+    B, Sq, H, D = q.shape
+    num_blocks, bs, Hkv, _ = k_pool.shape
+    max_blocks = block_table.shape[1]
+    if Hkv == 0 or H % Hkv != 0:
+        raise PliError(f"heads {H} not a multiple of kv heads {Hkv}")
+    cap = max_blocks * bs
+    max_kv = cap if max_kv is None else int(max_kv)
+    if not 0 <= max_kv <= cap:
+        raise PliError(f"max_kv {max_kv} outside the table row [0, {cap}]")
+    if out is None:
+        out = torch.empty((B, Sq, H, D), device=q.device, dtype=q.dtype)
+    _require_gpu(q, out)
+    if tuple(out.shape) != (B, Sq, H, D) or (out.numel() and out.stride(-1) != 1):
+        raise PliError("bad output tensor")
+    if scale is None:
+        scale = D ** -0.5
+    st = (_c_i64 * 12)(*(int(x) for x in (q.stride(0), q.stride(2), q.stride(1),
+                                          k_pool.stride(0), k_pool.stride(1), k_pool.stride(2),
+                                          v_pool.stride(0), v_pool.stride(1), v_pool.stride(2),
+                                          out.stride(0), out.stride(2), out.stride(1))))
+    ws_bytes = int(lib().pli_attn_decode_paged_workspace_size(B, H, Hkv, Sq, max_kv, D))
+    if workspace is None or workspace.numel() * workspace.element_size() < ws_bytes:
+        workspace = torch.empty(max(ws_bytes // 4, 1), device=q.device, dtype=torch.float32)
+    with _on_device(dev):
+        rc = lib().pli_attn_decode_paged(_ptr(q), _ptr(k_pool), _ptr(v_pool), _ptr(out), _ptr(block_table),
+                                         _ptr(seq_lens), B, H, Hkv, Sq, D, bs, num_blocks, max_blocks, max_kv,
+                                         st, float(scale), int(bool(causal)), int(n_kv_add), _ptr(workspace),
+                                         ws_bytes, _dtype_code(q), _stream(dev))
+    _check(rc, "pli_attn_decode_paged")
+    return out
+
+
+def kv_append_paged(k_new: torch.Tensor, v_new: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor,
+                    block_table: torch.Tensor, seq_lens: torch.Tensor) -> None:
+    """Write token t of k_new / v_new [B, T, Hkv, D] of sequence b to logical
+    position seq_lens[b] + t of the paged pools, through block_table (positions
+    past the table row are dropped).  seq_lens is not advanced: the caller adds
+    T on the device (seq_lens.add_(T)), which a graph capture records too."""
+    dev = _check_paged("kv_append_paged", k_new, k_pool, v_pool, block_table, seq_lens)
+    _require_gpu(k_new, v_new)
+    B, T, Hkv, D = k_new.shape
+    if tuple(v_new.shape) != tuple(k_new.shape) or k_pool.shape[2] != Hkv or (v_new.numel() and v_new.stride(-1) != 1):
+        raise PliError(f"kv_append_paged shape mismatch new{tuple(k_new.shape)} v{tuple(v_new.shape)} "
+                       f"pool{tuple(k_pool.shape)}")
+    num_blocks, bs = k_pool.shape[0], k_pool.shape[1]
+    st = (_c_i64 * 12)(*(int(x) for x in (k_new.stride(0), k_new.stride(2), k_new.stride(1),
+                                          k_pool.stride(0), k_pool.stride(1), k_pool.stride(2),
+                                          v_pool.stride(0), v_pool.stride(1), v_pool.stride(2),
+                                          v_new.stride(0), v_new.stride(2), v_new.stride(1))))
+    with _on_device(dev):
+        rc = lib().pli_kv_append_paged(_ptr(k_new), _ptr(v_new), _ptr(k_pool), _ptr(v_pool), _ptr(block_table),
+                                       _ptr(seq_lens), B, T, Hkv, D, bs, num_blocks, block_table.shape[1], st,
+                                       _dtype_code(k_new), _stream(dev))
+    _check(rc, "pli_kv_append_paged")
 
 
 # ---------------------------------------------------------------------- MoE
