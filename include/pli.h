@@ -413,6 +413,63 @@ int pli_kv_append_paged(const void* k_new, const void* v_new, void* k_pool,
                         int num_blocks, int max_blocks_per_seq,
                         const int64_t* strides, int dtype, void* stream);
 
+/* Packed variable-length attention over the same paged pool: one call for a
+ * step in which every sequence brings its own number of new tokens (prompt
+ * chunks, decode rows, sequences that sit the step out).  The kernel the
+ * reference's ch08 text assumes ("process all in single forward pass ...
+ * FlashAttention handles both cases") and never writes.
+ *
+ * q / o: packed [max_tokens, heads, head_dim].  cu_seqlens_q: device int32
+ *   [batch + 1]; sequence b owns packed tokens cu[b] .. cu[b+1] - 1,
+ *   q_len(b) = max(0, cu[b+1] - cu[b]); a q_len of 0 sits the step out.
+ * seq_lens[b]: the kv length AFTER this step's tokens are in the pool;
+ *   n_kv(b) = clamp(seq_lens[b], 0, max_kv).  block_table and the pools are
+ *   those of pli_attn_decode_paged.
+ * pli_attn_varlen_paged: strides[10] in elements: {q_t, q_h, k_page, k_token,
+ *   k_head, v_page, v_token, v_head, o_t, o_h}.  causal masks bottom-right:
+ *   token i of sequence b sees keys j <= n_kv(b) - q_len(b) + i; causal == 0:
+ *   every key below n_kv(b).  A row that sees no key (n_kv < q_len among them)
+ *   is written as 0; packed rows >= min(cu[batch], max_tokens) are not written.
+ *   cu_seqlens_q, block_table and seq_lens are read on the device; the grid
+ *   depends on (batch, max_tokens, heads, kv_heads) only; nothing is allocated
+ *   or synchronised and there is no workspace, so the call replays in a
+ *   captured graph while the three tensors change in place.  Every address is
+ *   clamped into its operand whatever the three tensors hold.
+ *   The MFMA kernel attn_varlen_paged takes bf16/fp16, D in {64, 128},
+ *   heads/kv_heads in {1, 2, 4, 8, 16}, a power-of-two block_size >= 16,
+ *   scale > 0, strides % 8 == 0 and 16-byte aligned operands; everything else
+ *   (fp32, head_dim <= 256, any block_size, any group size) runs
+ *   attn_varlen_paged_generic, a correctness path.  pli_last_route names one
+ *   of the two.
+ * pli_kv_append_varlen_paged: token i of sequence b (packed row cu[b] + i of
+ *   k_new / v_new [max_tokens, Hkv, D]) goes to logical position
+ *   seq_lens[b] - q_len(b) + i; negative positions and positions >=
+ *   max_blocks_per_seq * block_size are dropped.  It takes the same three
+ *   device tensors as the attention call.  strides[10] in elements: {kn_t,
+ *   kn_h, k_page, k_token, k_head, v_page, v_token, v_head, vn_t, vn_h}; rows of
+ *   whole 16-byte chunks as for pli_kv_append_paged.  pli_last_route:
+ *   "kv_append_varlen_paged".
+ * PLI_EINVAL before any HIP call as for the paged entry points above; an
+ * empty call (batch == 0 or max_tokens == 0) returns PLI_OK and its operands
+ * may be NULL. */
+int pli_attn_varlen_paged(const void* q, const void* k_pool, const void* v_pool,
+                          void* o, const int32_t* cu_seqlens_q,
+                          const int32_t* block_table, const int32_t* seq_lens,
+                          int batch, int max_tokens, int heads, int kv_heads,
+                          int head_dim, int block_size, int num_blocks,
+                          int max_blocks_per_seq, int max_kv,
+                          const int64_t* strides, float scale, int causal,
+                          int dtype, void* stream);
+int pli_kv_append_varlen_paged(const void* k_new, const void* v_new,
+                               void* k_pool, void* v_pool,
+                               const int32_t* cu_seqlens_q,
+                               const int32_t* block_table,
+                               const int32_t* seq_lens, int batch,
+                               int max_tokens, int kv_heads, int head_dim,
+                               int block_size, int num_blocks,
+                               int max_blocks_per_seq, const int64_t* strides,
+                               int dtype, void* stream);
+
 /* ------------------------------------------------------------------------
  * Tuning section: the same operations with an explicit kernel choice, for
  * A/B runs (tools/tune.py) and the per-variant parity tests.  Not part of

@@ -18,7 +18,11 @@ attended over in place, through ``pli_kv_append_paged`` and
 * ``append(layer, k_new, v_new, block_table, seq_lens)`` stores the newest
   tokens of every sequence,
 * ``attend(layer, q, block_table, seq_lens)`` runs decode attention over each
-  sequence's own pages and length.
+  sequence's own pages and length,
+* ``tables_packed`` / ``append_packed`` / ``attend_packed`` do the same for a
+  mixed step -- every request brings its own number of new tokens, packed
+  behind a ``cu_seqlens_q`` -- through ``pli_kv_append_varlen_paged`` and
+  ``pli_attn_varlen_paged`` (csrc/varlen_attn.hip), one launch each.
 
 No page is gathered into a contiguous tensor on the way.
 """
@@ -160,6 +164,39 @@ class PagedKVCache:
         return pli_hip.attn_decode_paged(q, k_pool, v_pool, block_table, seq_lens, causal=causal,
                                          n_kv_add=n_kv_add)
 
+    # ------------------------------------------- packed (mixed) steps --
+    def tables_packed(self, request_ids, new_tokens, max_blocks: int | None = None):
+        """(block_table, seq_lens, cu_seqlens_q) of a step in which request i
+        brings ``new_tokens[i]`` tokens (any count, 0 for a request that sits the
+        step out): ``tables(request_ids, max_blocks)`` plus cu_seqlens_q int32
+        [B + 1], the running sum of new_tokens, so request i owns packed rows
+        cu[i] .. cu[i+1] - 1.  seq_lens already counts the new tokens: the
+        order of a step is extend_blocks(rid, n), tables_packed, append_packed,
+        attend_packed."""
+        new_tokens = [int(n) for n in new_tokens]
+        if len(new_tokens) != len(request_ids) or any(n < 0 for n in new_tokens):
+            raise ValueError("new_tokens needs one non-negative count per request")
+        table, lens = self.tables(request_ids, max_blocks)
+        cu = torch.tensor([0] + new_tokens, dtype=torch.int64).cumsum(0).to(torch.int32)
+        return table, lens, cu.to(table.device)
+
+    def append_packed(self, layer: int, k_new: torch.Tensor, v_new: torch.Tensor, block_table: torch.Tensor,
+                      seq_lens: torch.Tensor, cu_seqlens_q: torch.Tensor) -> None:
+        """Store packed k_new / v_new [tokens, heads, head_dim] as the LAST
+        tokens of their sequences: row cu[b] + i goes to position
+        seq_lens[b] - (cu[b+1] - cu[b]) + i."""
+        k_pool, v_pool = self._pools(layer)
+        pli_hip.kv_append_varlen_paged(k_new, v_new, k_pool, v_pool, block_table, seq_lens, cu_seqlens_q)
+
+    def attend_packed(self, layer: int, q: torch.Tensor, block_table: torch.Tensor, seq_lens: torch.Tensor,
+                      cu_seqlens_q: torch.Tensor, causal: bool = True) -> torch.Tensor:
+        """Attention of packed q [tokens, Hq, head_dim] over each sequence's
+        own pages and length in one launch, prompt chunks and decode rows
+        mixed; causal masks bottom-right per sequence.  Returns [tokens, Hq,
+        head_dim]."""
+        k_pool, v_pool = self._pools(layer)
+        return pli_hip.attn_varlen_paged(q, k_pool, v_pool, block_table, seq_lens, cu_seqlens_q, causal=causal)
+
 
 def explain_paged_memory() -> str:
     return """
@@ -183,6 +220,15 @@ Attention over pages:
   - The table entries a step needs are fetched two steps ahead, so the extra
     indirection stays off the critical path; every sequence attends over its
     own length, read on the device, so the step replays in a captured graph.
+
+Mixed steps (prompt chunks and decode rows in one launch):
+  - pli_attn_varlen_paged takes the step's new tokens packed, sequence b
+    owning rows cu_seqlens_q[b] .. cu_seqlens_q[b+1] - 1, however many each
+    has (none for a request that sits the step out).
+  - 64 rows of one kv head (token-major, the kv head's query heads minor) form
+    a tile; the four waves of a workgroup share each 32-key K/V image, loaded
+    once through the block table, and a tile stops at its last row's causal
+    limit.  tables_packed / append_packed / attend_packed drive it.
 """
 
 

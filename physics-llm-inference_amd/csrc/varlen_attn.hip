@@ -1,0 +1,510 @@
+// Packed variable-length causal attention over the paged KV pool, and the
+// packed append that feeds it, for gfx950: one launch for a step in which
+// every sequence brings its own number of new tokens (prompt chunks, decode
+// rows and sequences that sit the step out, mixed).
+//
+// attn_varlen_paged<T, D> keeps the MFMA dataflow of attn_decode_paged
+// (paged_attn.hip): S^T = K . Q^T and O^T += V^T . P^T by
+// v_mfma_f32_16x16x32, fp32 statistics, 16 query rows per wave.  The roles of
+// the waves change:
+//   * a workgroup is one tile of VAR_BM = 64 rows of one kv head; row r of a
+//     sequence is (token r / G, head hk*G + r % G), so a decode row group reads
+//     its keys once per kv head and a prompt chunk fills the tile with 64 / G
+//     tokens.  Workgroup w finds its (sequence, tile) from cu_seqlens_q with
+//     the rule of varlen_plan.h (one load round per 256 sequences: each lane
+//     sums a slice of 4 sequences, the wave prefix-sums the slices) or finds
+//     nothing and exits.  The grid depends on (batch, max_tokens, heads,
+//     kv_heads) only.
+//   * the 4 waves hold the tile's four 16-row groups and share one K/V LDS image
+//     per 32-key step.  All 256 threads load the step through the block table
+//     (whole-row 16-byte loads, registers, then LDS); the image is
+//     double-buffered and the loads run two steps ahead of the MFMAs (two
+//     register stages), with one barrier per step.  Each wave keeps its own
+//     running max / sum / O: there is no merge at the end.
+//   * a 16-key group of a step lies in one page (power-of-two block size >=
+//     16), and the lanes of a wave load rows of one group per pass, so the table
+//     entry is wave-uniform; the entries of step t + 3 are fetched while step t
+//     computes, a step ahead of the loads that use them.
+//   * a tile walks keys [0, key_end), key_end one past its last row's causal
+//     limit; only steps that cross a row's limit apply the mask.  A wave none
+//     of whose rows exist (a decode tile) loads and synchronises but skips the
+//     MFMAs.
+//   * every address is clamped (token into [0, max_tokens - 1], key to the
+//     sequence's last key, block into the table row, page into the pool) and the
+//     masks are applied afterwards; stores are predicated.
+// attn_varlen_paged_generic covers every other case (fp32, other head dims,
+// any block size, any group size): one wave per packed (token, head) row,
+// modelled on attn_decode_paged_generic -- a correctness path, not tuned.
+// kv_append_varlen_paged_kernel: one thread per 16-byte chunk of a packed
+// token's K and V row.
+#include <cmath>
+
+#include "pli_common.h"
+#include "varlen_plan.h"
+
+namespace pli {
+namespace {
+
+inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// element strides: q / o {token, head}; pools {page, token, head}
+struct VarStrides {
+    int64_t qt, qh, ot, oh;
+    PagedPool k, v;
+};
+
+template <int D> struct VarLayout {
+    static constexpr int KS = 2 * D + 16;  // K row stride in LDS (bytes)
+    static constexpr int VS = 2 * D + 32;  // V row stride in LDS (bytes)
+    static constexpr int KBYTES = VAR_STEP * KS;
+    static constexpr int IMAGE = KBYTES + VAR_STEP * VS;  // one step's K + V
+    static constexpr int LDS = 2 * IMAGE;
+};
+
+// workgroup w -> (sequence, tile), every lane of the calling wave gets the
+// same answer: varlen_find_tile of varlen_plan.h spread over the 64 lanes
+__device__ __forceinline__ VarTile find_tile_wave(const int32_t* __restrict__ cu, int batch, int tpt,
+                                                  int64_t cap, int64_t w, int lane) {
+    int64_t before = 0;
+    for (int base = 0; base < batch; base += VAR_SLICE * VAR_LANES) {
+        const int first = base + VAR_SLICE * lane;
+        const int64_t n = varlen_slice_tiles(cu, batch, first, tpt, cap);
+        int64_t incl = n;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int64_t up = __shfl_up(incl, o, 64);
+            if (lane >= o) incl += up;
+        }
+        const int64_t lo = before + incl - n;
+        const bool hit = w >= lo && w < lo + n;
+        const unsigned long long votes = __ballot(hit);
+        if (votes) {
+            const int src = __ffsll((long long)votes) - 1;
+            const int64_t lo_src = __shfl(lo, src, 64);
+            return varlen_find_in_slice(cu, batch, base + VAR_SLICE * src, tpt, cap, w - lo_src);
+        }
+        before += __shfl(incl, 63, 64);
+    }
+    return VarTile{-1, 0};
+}
+
+template <typename T, int D>
+__global__ __launch_bounds__(256, 2) void attn_varlen_paged(
+    const uint16_t* __restrict__ q, const uint16_t* __restrict__ k, const uint16_t* __restrict__ v,
+    uint16_t* __restrict__ o, const int32_t* __restrict__ cu, const int32_t* __restrict__ table,
+    const int32_t* __restrict__ seq_lens, int batch, int max_tokens, int Hkv, int G, VarStrides st,
+    PagedTable tb, float c, int causal, int max_kv, int tiles_upper) {
+    using L = VarLayout<D>;
+    constexpr int KSTEPS = D / 32;  // 32-d k-steps of K.Q^T
+    constexpr int DB = D / 16;      // 16-d blocks of O
+    __shared__ __attribute__((aligned(16))) char smem[L::LDS];
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l16 = lane & 15, g = lane >> 4;
+    // block order: (tile, hk) with the kv head innermost, so co-resident
+    // workgroups sweep the same pages of all heads
+    const int hk = blockIdx.x % Hkv;
+    const int w = blockIdx.x / Hkv;
+    const int tpt = VAR_BM / G;
+    const VarTile found = find_tile_wave(cu, batch, tpt, tiles_upper, w, lane);
+    const int b = __builtin_amdgcn_readfirstlane(found.b);
+    if (b < 0) return;  // every wave finds the same answer: the whole workgroup leaves
+    const int tile = __builtin_amdgcn_readfirstlane(found.tile);
+    const int cu_b = cu[b];
+    const int q_len = varlen_q_len(cu_b, cu[b + 1]);
+    const int live = varlen_tokens_live(cu[batch], max_tokens);
+    const int Nk = varlen_n_kv(seq_lens[b], max_kv);
+    const int key_end = varlen_key_end(Nk, q_len, tile, tpt, causal);
+    const int nsteps = cdiv(key_end, VAR_STEP);
+
+    // this lane's query row: MFMA column l16 of the wave's 16-row group
+    const int r = wave * VAR_ROWS + l16;
+    const int64_t qi = (int64_t)tile * tpt + r / G;
+    const int hq = hk * G + r % G;
+    const bool row_ok = qi < q_len;
+    // a wave with no row at all (rows are dense from 0) skips the MFMAs
+    const bool wave_on = __builtin_amdgcn_readfirstlane((int64_t)tile * tpt + (wave * VAR_ROWS) / G < q_len ? 1 : 0) != 0;
+    const int tok = varlen_token(cu_b, qi, max_tokens);
+    i32x4 qf[KSTEPS];
+    {
+        const uint16_t* src = q + (int64_t)tok * st.qt + (int64_t)hq * st.qh + 8 * g;
+#pragma unroll
+        for (int ks = 0; ks < KSTEPS; ++ks) {
+            const i32x4 x = *reinterpret_cast<const i32x4*>(src + 32 * ks);
+            qf[ks] = row_ok ? x : i32x4{0, 0, 0, 0};
+        }
+    }
+    // last key this row sees (bottom-right causal per sequence); < 0: none
+    const int hi = row_ok ? varlen_row_limit(Nk, q_len, (int)qi, causal) : -1;
+
+    // cooperative row-major loads: thread loads 16-byte chunk rch of step row
+    // i*RPP + rrow in pass i; the rows of a wave in a pass lie in one 16-key group
+    constexpr int CPR = D / 8, RPP = 256 / CPR, PASSES = VAR_STEP / RPP;
+    const int rrow = tid / CPR, rch = tid % CPR;
+    const uint16_t* kp = k + 8 * rch;
+    const uint16_t* vp = v + 8 * rch;
+    // plain loads: the other tiles of the sequence re-read these rows from L2
+    auto ld = [](const uint16_t* p) { return *reinterpret_cast<const i32x4*>(p); };
+    // raw table entries of the wave's group of each pass: clamping here would
+    // wait for the load at once
+    auto pages = [&](int key0, int (&e)[PASSES]) {
+#pragma unroll
+        for (int i = 0; i < PASSES; ++i) {
+            const int grp = (i * RPP + wave * (64 / CPR)) / 16;
+            e[i] = table[paged_table_index(b, varlen_group_block(key0, grp, Nk, tb), tb)];
+        }
+    };
+    auto load_step = [&](int key0, const int (&e)[PASSES], i32x4 (&kr)[PASSES], i32x4 (&vr)[PASSES]) {
+#pragma unroll
+        for (int i = 0; i < PASSES; ++i) {
+            const int key = varlen_load_key(key0, i * RPP + rrow, Nk);
+            kr[i] = ld(kp + varlen_kv_offset(e[i], key, hk, tb, st.k));
+            vr[i] = ld(vp + varlen_kv_offset(e[i], key, hk, tb, st.v));
+        }
+    };
+    const int kw = rrow * L::KS + rch * 16;                     // K row-major write
+    const int vw = rrow * L::VS + rch * 16;
+    auto store_step = [&](char* img, const i32x4 (&kr)[PASSES], const i32x4 (&vr)[PASSES]) {
+#pragma unroll
+        for (int i = 0; i < PASSES; ++i) {
+            lds_write_b128(img + L::KBYTES, vw + i * RPP * L::VS, vr[i]);
+            lds_write_b128(img, kw + i * RPP * L::KS, kr[i]);
+        }
+    };
+    const int kr_off = l16 * L::KS + g * 16;                    // K fragment read
+    const int qq = l16 >> 2, pp = lane & 3;
+    const int vr_off = (4 * g + qq) * L::VS + 8 * pp;           // tr read: key 4g+qq, col 4pp
+
+    f32x4 oacc[DB];
+#pragma unroll
+    for (int d = 0; d < DB; ++d) oacc[d] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float m_run = -1e30f, l_run = 0.f;
+
+    // one 32-key step of this wave's 16 rows on the image at `img`
+    auto compute = [&](const char* img, int key0) {
+        const char* kt = img;
+        const char* vt = img + L::KBYTES;
+        f32x4 s[2];
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) {
+            s[kb] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < KSTEPS; ++ks) {
+                const i32x4 kf = lds_read_b128(kt, kr_off + 16 * kb * L::KS + 64 * ks);
+                s[kb] = mfma16x16x32<T>(kf, qf[ks], s[kb]);
+            }
+        }
+        // mask only where the step crosses this row's limit (or n_kv)
+        if (key0 + VAR_STEP - 1 > hi) {
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                for (int rr = 0; rr < 4; ++rr)
+                    if (key0 + 16 * kb + 4 * g + rr > hi) s[kb][rr] = -INFINITY;
+        }
+        float mx = max3(s[0][0], s[0][1], s[0][2]);
+        mx = max3(mx, s[0][3], s[1][0]);
+        mx = max3(mx, s[1][1], s[1][2]);
+        mx = fmaxf(mx, s[1][3]);
+        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        const float m_new = fmaxf(m_run, mx * c);
+        const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+        m_run = m_new;
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) s[kb][rr] = __builtin_amdgcn_exp2f(fmaf(s[kb][rr], c, -m_new));
+        const uint32_t p0 = pack2<T>(s[0][0], s[0][1]), p1 = pack2<T>(s[0][2], s[0][3]);
+        const uint32_t p2 = pack2<T>(s[1][0], s[1][1]), p3 = pack2<T>(s[1][2], s[1][3]);
+        const i32x4 pb = {(int)p0, (int)p1, (int)p2, (int)p3};
+        l_run = fmaf(l_run, alpha, add_pair<T>(p0, add_pair<T>(p1, add_pair<T>(p2, add_pair<T>(p3, 0.f)))));
+#pragma unroll
+        for (int d = 0; d < DB; ++d) {
+            const i32x2 lo = lds_read_tr16(vt, vr_off + 32 * d);
+            const i32x2 hi2 = lds_read_tr16(vt, vr_off + 32 * d + 16 * L::VS);
+            oacc[d] = mfma16x16x32<T>(i32x4{lo.x, lo.y, hi2.x, hi2.y}, pb, oacc[d] * alpha);
+        }
+    };
+
+    // Pipeline.  Iteration t: issue step t+2's loads into the free register
+    // stage (entries fetched an iteration ago), fetch step t+3's entries,
+    // compute step t from image t & 1, write step t+1's registers into the other
+    // image, barrier.  The barrier at the end of iteration t-1 is what makes the
+    // other image free to overwrite and this one complete to read.
+    // The loads and the LDS writes of steps past the last one are NOT skipped:
+    // their addresses are clamped like any other (they re-read the sequence's
+    // last key) and nobody reads what they write.  Behind a condition, the
+    // compiler's wait-count pass sees a path on which a register stage is still
+    // in flight when its registers are reused, and waits for every outstanding
+    // load before it issues the next step's -- which puts the whole memory
+    // latency back into each step.
+    i32x4 ka[PASSES], va[PASSES], kb2[PASSES], vb2[PASSES];
+    int pn[PASSES];
+    auto body = [&](int t, int cur, i32x4 (&kfree)[PASSES], i32x4 (&vfree)[PASSES], i32x4 (&knext)[PASSES],
+                    i32x4 (&vnext)[PASSES]) {
+        int pf[PASSES];
+        pages((t + 3) * VAR_STEP, pf);
+        load_step((t + 2) * VAR_STEP, pn, kfree, vfree);
+#pragma unroll
+        for (int i = 0; i < PASSES; ++i) pn[i] = pf[i];
+        if (wave_on && t < nsteps) compute(smem + cur * L::IMAGE, t * VAR_STEP);
+        store_step(smem + (cur ^ 1) * L::IMAGE, knext, vnext);
+        __syncthreads();
+    };
+    if (nsteps > 0) {
+        int p0[PASSES], p1[PASSES];
+        pages(0, p0);
+        pages(VAR_STEP, p1);
+        pages(2 * VAR_STEP, pn);
+        load_step(0, p0, ka, va);
+        load_step(VAR_STEP, p1, kb2, vb2);
+        store_step(smem, ka, va);
+        __syncthreads();
+    }
+    // two steps per trip (the register stages swap roles).  With an odd step
+    // count the last trip's second half loads, writes and synchronises but does
+    // not compute: the loop has one exit, so no path re-enters the first half
+    // with its register stage in flight (see above).
+    for (int t = 0; t < nsteps; t += 2) {
+        body(t, 0, ka, va, kb2, vb2);
+        body(t + 1, 1, kb2, vb2, ka, va);
+    }
+
+    // row sum over the 4 lane groups holding the row
+    l_run += __shfl_xor(l_run, 16, 64);
+    l_run += __shfl_xor(l_run, 32, 64);
+    if (!varlen_row_stored(cu_b, qi, q_len, live)) return;
+    // a row that saw no key (n_kv < q_len rows, an empty sequence) has l = 0: written as 0
+    const float inv = l_run > 0.f ? 1.f / l_run : 0.f;
+    // O^T block d: this lane holds dims 16d + 4g .. + 3 of row l16
+    uint16_t* op = o + (int64_t)tok * st.ot + (int64_t)hq * st.oh + 4 * g;
+#pragma unroll
+    for (int d = 0; d < DB; ++d)
+        *reinterpret_cast<i32x2*>(op + 16 * d) = i32x2{(int)pack2<T>(oacc[d][0] * inv, oacc[d][1] * inv),
+                                                        (int)pack2<T>(oacc[d][2] * inv, oacc[d][3] * inv)};
+}
+
+// Any dtype, head_dim <= 256, any block size, any group size: one wave per
+// packed (token, head) row; lane l owns dims l, l + 64, ...; keys in order,
+// fp32 online softmax.  Correctness path only.
+constexpr int VGEN_MAXD = 256, VGEN_DPL = VGEN_MAXD / 64;
+template <typename T>
+__global__ __launch_bounds__(64) void attn_varlen_paged_generic(
+    const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, T* __restrict__ o,
+    const int32_t* __restrict__ cu, const int32_t* __restrict__ table, const int32_t* __restrict__ seq_lens,
+    int batch, int max_tokens, int H, int G, int D, VarStrides st, PagedTable tb, float scale, int causal,
+    int max_kv) {
+    const int lane = threadIdx.x;
+    const int h = blockIdx.x % H;
+    const int t = blockIdx.x / H;
+    if (t >= varlen_tokens_live(cu[batch], max_tokens)) return;
+    const int b = varlen_owner(cu, batch, t);
+    if (b < 0) return;
+    const int hk = h / G;
+    const int q_len = varlen_q_len(cu[b], cu[b + 1]);
+    const int Nk = varlen_n_kv(seq_lens[b], max_kv);
+    const int nvis = varlen_row_limit(Nk, q_len, t - cu[b], causal) + 1;
+    const T* qrow = q + (int64_t)t * st.qt + (int64_t)h * st.qh;
+    float qv[VGEN_DPL], acc[VGEN_DPL];
+#pragma unroll
+    for (int i = 0; i < VGEN_DPL; ++i) {
+        const int d = lane + 64 * i;
+        qv[i] = d < D ? elem<T>::to_f32(qrow[d]) : 0.f;
+        acc[i] = 0.f;
+    }
+    float m = -INFINITY, l = 0.f;
+    for (int j = 0; j < nvis; ++j) {
+        const T* krow = k + paged_key_offset(table, b, j, hk, tb, st.k);
+        const T* vrow = v + paged_key_offset(table, b, j, hk, tb, st.v);
+        float dot = 0.f;
+#pragma unroll
+        for (int i = 0; i < VGEN_DPL; ++i) {
+            const int d = lane + 64 * i;
+            if (d < D) dot = fmaf(qv[i], elem<T>::to_f32(krow[d]), dot);
+        }
+        const float s = wave_sum(dot) * scale;
+        const float m_new = fmaxf(m, s);
+        const float a = __expf(m - m_new), p = __expf(s - m_new);
+        l = fmaf(l, a, p);
+#pragma unroll
+        for (int i = 0; i < VGEN_DPL; ++i) {
+            const int d = lane + 64 * i;
+            if (d < D) acc[i] = fmaf(acc[i], a, p * elem<T>::to_f32(vrow[d]));
+        }
+        m = m_new;
+    }
+    const float inv = l > 0.f ? 1.f / l : 0.f;  // no visible key: O = 0
+    T* orow = o + (int64_t)t * st.ot + (int64_t)h * st.oh;
+#pragma unroll
+    for (int i = 0; i < VGEN_DPL; ++i) {
+        const int d = lane + 64 * i;
+        if (d < D) orow[d] = elem<T>::from_f32(acc[i] * inv);
+    }
+}
+
+// Packed append: one thread per 16-byte chunk of packed token t's K and V row
+// of one head; the token's owner comes from cu_seqlens_q, its position from
+// varlen_append_pos.  Every stride here is in bytes.
+struct VarAppendStrides {
+    int64_t kt, kh, vt, vh;  // the new tensors: token, head
+    PagedPool k, v;
+};
+__global__ __launch_bounds__(256) void kv_append_varlen_paged_kernel(
+    const char* __restrict__ kn, const char* __restrict__ vn, char* __restrict__ kpool,
+    char* __restrict__ vpool, const int32_t* __restrict__ cu, const int32_t* __restrict__ table,
+    const int32_t* __restrict__ seq_lens, int batch, int max_tokens, int Hkv, int cpr, VarAppendStrides st,
+    PagedTable tb) {
+    const int64_t total = (int64_t)max_tokens * Hkv * cpr;
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int ch = idx % cpr;
+    const int h = (idx / cpr) % Hkv;
+    const int t = (int)(idx / ((int64_t)cpr * Hkv));
+    if (t >= varlen_tokens_live(cu[batch], max_tokens)) return;
+    const int b = varlen_owner(cu, batch, t);
+    if (b < 0) return;
+    const int64_t pos = varlen_append_pos(seq_lens[b], varlen_q_len(cu[b], cu[b + 1]), t - cu[b],
+                                          (int64_t)tb.max_blocks_per_seq * tb.block_size);
+    if (pos < 0) return;
+    const char* ks = kn + (int64_t)t * st.kt + (int64_t)h * st.kh + 16 * ch;
+    const char* vs = vn + (int64_t)t * st.vt + (int64_t)h * st.vh + 16 * ch;
+    char* kd = kpool + paged_key_offset(table, b, (int)pos, h, tb, st.k) + 16 * ch;
+    char* vd = vpool + paged_key_offset(table, b, (int)pos, h, tb, st.v) + 16 * ch;
+    *reinterpret_cast<i32x4*>(kd) = *reinterpret_cast<const i32x4*>(ks);
+    *reinterpret_cast<i32x4*>(vd) = *reinterpret_cast<const i32x4*>(vs);
+}
+
+struct VarCall {
+    const void *q, *k, *v;
+    void* o;
+    const int32_t *cu, *table, *seq_lens;
+    int B, T, H, Hkv, D, max_kv, causal;
+    VarStrides st;
+    PagedTable tb;
+    float scale;
+    hipStream_t stream;
+};
+
+template <typename T, int D>
+int launch_varlen(const VarCall& a, int64_t tiles_upper) {
+    const float c = a.scale * 1.4426950408889634f;
+    hipLaunchKernelGGL((attn_varlen_paged<T, D>), dim3((unsigned)(tiles_upper * a.Hkv)), dim3(256), 0, a.stream,
+                       (const uint16_t*)a.q, (const uint16_t*)a.k, (const uint16_t*)a.v, (uint16_t*)a.o, a.cu,
+                       a.table, a.seq_lens, a.B, a.T, a.Hkv, a.H / a.Hkv, a.st, a.tb, c, a.causal, a.max_kv,
+                       (int)tiles_upper);
+    return launch_status("attn_varlen_paged");
+}
+
+template <typename T>
+int launch_varlen_generic(const VarCall& a) {
+    hipLaunchKernelGGL((attn_varlen_paged_generic<T>), dim3((unsigned)((int64_t)a.T * a.H)), dim3(64), 0, a.stream,
+                       (const T*)a.q, (const T*)a.k, (const T*)a.v, (T*)a.o, a.cu, a.table, a.seq_lens, a.B, a.T,
+                       a.H, a.H / a.Hkv, a.D, a.st, a.tb, a.scale, a.causal, a.max_kv);
+    return launch_status("attn_varlen_paged_generic");
+}
+
+}  // namespace
+}  // namespace pli
+
+extern "C" int pli_attn_varlen_paged(const void* q, const void* k_pool, const void* v_pool, void* o,
+                                     const int32_t* cu_seqlens_q, const int32_t* block_table,
+                                     const int32_t* seq_lens, int batch, int max_tokens, int heads,
+                                     int kv_heads, int head_dim, int block_size, int num_blocks,
+                                     int max_blocks_per_seq, int max_kv, const int64_t* strides, float scale,
+                                     int causal, int dtype, void* stream) {
+    using namespace pli;
+    clear_error();
+    PLI_REQUIRE(batch >= 0 && max_tokens >= 0 && heads > 0 && kv_heads > 0 && head_dim > 0 && num_blocks >= 0 &&
+                    max_blocks_per_seq >= 0 && max_kv >= 0,
+                "pli_attn_varlen_paged: bad shape B=%d tokens=%d H=%d Hkv=%d D=%d blocks=%d "
+                "max_blocks_per_seq=%d max_kv=%d",
+                batch, max_tokens, heads, kv_heads, head_dim, num_blocks, max_blocks_per_seq, max_kv);
+    PLI_REQUIRE(heads % kv_heads == 0, "pli_attn_varlen_paged: heads %d not a multiple of kv_heads %d", heads,
+                kv_heads);
+    PLI_REQUIRE(dtype == PLI_F32 || dtype == PLI_F16 || dtype == PLI_BF16, "pli_attn_varlen_paged: bad dtype %d",
+                dtype);
+    PLI_REQUIRE(std::isfinite(scale), "pli_attn_varlen_paged: non-finite scale");
+    PLI_REQUIRE(block_size > 0, "pli_attn_varlen_paged: block_size %d must be positive", block_size);
+    PLI_REQUIRE((int64_t)max_kv <= (int64_t)max_blocks_per_seq * block_size,
+                "pli_attn_varlen_paged: max_kv %d past the table row (%d blocks of %d tokens)", max_kv,
+                max_blocks_per_seq, block_size);
+    PLI_REQUIRE((int64_t)max_blocks_per_seq * block_size < (1ll << 31),
+                "pli_attn_varlen_paged: a table row of %d blocks x %d tokens passes 2^31 keys", max_blocks_per_seq,
+                block_size);
+    // no output rows: the (possibly NULL, pli.h) operands are not read
+    if (batch == 0 || max_tokens == 0) return PLI_OK;
+    PLI_REQUIRE(q && o && k_pool && v_pool && cu_seqlens_q && block_table && seq_lens && strides,
+                "pli_attn_varlen_paged: null pointer");
+    PLI_REQUIRE(num_blocks > 0 && max_blocks_per_seq > 0,
+                "pli_attn_varlen_paged: empty pool or table (blocks=%d max_blocks_per_seq=%d)", num_blocks,
+                max_blocks_per_seq);
+    VarCall a;
+    a.q = q, a.k = k_pool, a.v = v_pool, a.o = o, a.cu = cu_seqlens_q, a.table = block_table, a.seq_lens = seq_lens;
+    a.B = batch, a.T = max_tokens, a.H = heads, a.Hkv = kv_heads, a.D = head_dim, a.max_kv = max_kv;
+    a.causal = causal != 0, a.scale = scale, a.stream = (hipStream_t)stream;
+    // strides[10] = {q_t, q_h, k_page, k_token, k_head, v_page, v_token, v_head, o_t, o_h}
+    a.st = VarStrides{strides[0], strides[1], strides[8], strides[9], PagedPool{strides[2], strides[3], strides[4]},
+                      PagedPool{strides[5], strides[6], strides[7]}};
+    a.tb = paged_table(block_size, num_blocks, max_blocks_per_seq);
+    const bool fast = varlen_fast_path(dtype, head_dim, heads, kv_heads, block_size, scale, strides,
+                                       aligned16(q) && aligned16(k_pool) && aligned16(v_pool) && aligned16(o));
+    if (!fast) {
+        PLI_REQUIRE(head_dim <= VGEN_MAXD, "pli_attn_varlen_paged: head_dim %d > %d", head_dim, VGEN_MAXD);
+        PLI_REQUIRE((int64_t)max_tokens * heads < (1ll << 31), "pli_attn_varlen_paged: grid too large");
+        if (dtype == PLI_F32) return launch_varlen_generic<float>(a);
+        return dtype == PLI_BF16 ? launch_varlen_generic<bf16_t>(a) : launch_varlen_generic<f16_t>(a);
+    }
+    const int64_t tiles_upper = varlen_tiles_upper(max_tokens, heads / kv_heads, batch);
+    PLI_REQUIRE(tiles_upper * kv_heads < (1ll << 31), "pli_attn_varlen_paged: grid too large");
+    if (dtype == PLI_BF16)
+        return head_dim == 128 ? launch_varlen<bf16_t, 128>(a, tiles_upper) : launch_varlen<bf16_t, 64>(a, tiles_upper);
+    return head_dim == 128 ? launch_varlen<f16_t, 128>(a, tiles_upper) : launch_varlen<f16_t, 64>(a, tiles_upper);
+}
+
+extern "C" int pli_kv_append_varlen_paged(const void* k_new, const void* v_new, void* k_pool, void* v_pool,
+                                          const int32_t* cu_seqlens_q, const int32_t* block_table,
+                                          const int32_t* seq_lens, int batch, int max_tokens, int kv_heads,
+                                          int head_dim, int block_size, int num_blocks, int max_blocks_per_seq,
+                                          const int64_t* strides, int dtype, void* stream) {
+    using namespace pli;
+    clear_error();
+    PLI_REQUIRE(batch >= 0 && max_tokens >= 0 && kv_heads > 0 && head_dim > 0 && num_blocks >= 0 &&
+                    max_blocks_per_seq >= 0,
+                "pli_kv_append_varlen_paged: bad shape B=%d tokens=%d Hkv=%d D=%d blocks=%d max_blocks_per_seq=%d",
+                batch, max_tokens, kv_heads, head_dim, num_blocks, max_blocks_per_seq);
+    PLI_REQUIRE(dtype == PLI_F32 || dtype == PLI_F16 || dtype == PLI_BF16,
+                "pli_kv_append_varlen_paged: bad dtype %d", dtype);
+    PLI_REQUIRE(block_size > 0, "pli_kv_append_varlen_paged: block_size %d must be positive", block_size);
+    PLI_REQUIRE((int64_t)max_blocks_per_seq * block_size < (1ll << 31),
+                "pli_kv_append_varlen_paged: a table row of %d blocks x %d tokens passes 2^31 keys",
+                max_blocks_per_seq, block_size);
+    // nothing to append: the (possibly NULL, pli.h) operands are not read
+    if (batch == 0 || max_tokens == 0) return PLI_OK;
+    PLI_REQUIRE(k_new && v_new && k_pool && v_pool && cu_seqlens_q && block_table && seq_lens && strides,
+                "pli_kv_append_varlen_paged: null pointer");
+    PLI_REQUIRE(num_blocks > 0 && max_blocks_per_seq > 0,
+                "pli_kv_append_varlen_paged: empty pool or table (blocks=%d max_blocks_per_seq=%d)", num_blocks,
+                max_blocks_per_seq);
+    const int es = dtype == PLI_F32 ? 4 : 2, per16 = 16 / es;
+    PLI_REQUIRE(head_dim % per16 == 0 && aligned16(k_new) && aligned16(v_new) && aligned16(k_pool) &&
+                    aligned16(v_pool),
+                "pli_kv_append_varlen_paged: 16-byte rows (head_dim %% %d) and 16-byte aligned operands required",
+                per16);
+    for (int i = 0; i < 10; ++i)
+        PLI_REQUIRE(strides[i] % per16 == 0, "pli_kv_append_varlen_paged: stride %d not a multiple of %d", i,
+                    per16);
+    const int cpr = head_dim / per16;
+    const int64_t total = (int64_t)max_tokens * kv_heads * cpr;
+    PLI_REQUIRE(cdiv64(total, 256) < (1ll << 31), "pli_kv_append_varlen_paged: grid too large");
+    // strides[10] = {kn_t, kn_h, k_page, k_token, k_head, v_page, v_token, v_head, vn_t, vn_h}
+    const VarAppendStrides st{strides[0] * es, strides[1] * es, strides[8] * es, strides[9] * es,
+                              PagedPool{strides[2] * es, strides[3] * es, strides[4] * es},
+                              PagedPool{strides[5] * es, strides[6] * es, strides[7] * es}};
+    hipLaunchKernelGGL(kv_append_varlen_paged_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0,
+                       (hipStream_t)stream, (const char*)k_new, (const char*)v_new, (char*)k_pool, (char*)v_pool,
+                       cu_seqlens_q, block_table, seq_lens, batch, max_tokens, kv_heads, cpr, st,
+                       paged_table(block_size, num_blocks, max_blocks_per_seq));
+    return launch_status("kv_append_varlen_paged");
+}

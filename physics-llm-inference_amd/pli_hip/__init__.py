@@ -83,6 +83,11 @@ _SIGS = {
                               _c_int, _vp, ctypes.c_size_t, _c_int, _vp],
     "pli_kv_append_paged": [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int,
                             _c_int, _c_int, ctypes.POINTER(_c_i64), _c_int, _vp],
+    "pli_attn_varlen_paged": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int,
+                              _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_i64), _c_f32, _c_int, _c_int,
+                              _vp],
+    "pli_kv_append_varlen_paged": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int,
+                                   _c_int, _c_int, ctypes.POINTER(_c_i64), _c_int, _vp],
     # tuning entry points (include/pli.h tuning section): explicit kernel variant
     "pli_flash_attn_fwd_variant": [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int,
                                    _c_int, ctypes.POINTER(_c_i64), _c_f32, _c_int, _c_int, _vp,
@@ -445,6 +450,98 @@ def kv_append_paged(k_new: torch.Tensor, v_new: torch.Tensor, k_pool: torch.Tens
                                        _ptr(seq_lens), B, T, Hkv, D, bs, num_blocks, block_table.shape[1], st,
                                        _dtype_code(k_new), _stream(dev))
     _check(rc, "pli_kv_append_paged")
+
+
+# ------------------------------------- packed variable-length paged attention
+def _check_varlen(what: str, x: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor,
+                  block_table: torch.Tensor, seq_lens: torch.Tensor, cu_seqlens_q: torch.Tensor):
+    """the checks of _check_paged for packed tokens: x is q or k_new
+    [max_tokens, H, D], cu_seqlens_q int32 [B + 1]; returns the device"""
+    dev = _require_gpu(x, k_pool, v_pool)
+    for name, t in (("block_table", block_table), ("seq_lens", seq_lens), ("cu_seqlens_q", cu_seqlens_q)):
+        if not t.is_cuda or t.device != dev or t.dtype != torch.int32 or not t.is_contiguous():
+            raise PliError(f"{what}: {name} must be a contiguous int32 tensor on {dev}")
+    if x.dim() != 3 or k_pool.dim() != 4 or tuple(v_pool.shape) != tuple(k_pool.shape):
+        raise PliError(f"{what} expects packed [tokens, H, D] rows and [num_blocks, block_size, Hkv, D] pools, got "
+                       f"{tuple(x.shape)} k{tuple(k_pool.shape)} v{tuple(v_pool.shape)}")
+    B, D = seq_lens.shape[0] if seq_lens.dim() == 1 else -1, x.shape[2]
+    if (k_pool.shape[3] != D or block_table.dim() != 2 or block_table.shape[0] != B or
+            tuple(cu_seqlens_q.shape) != (B + 1,)):
+        raise PliError(f"{what}: shape mismatch tokens{tuple(x.shape)} pool{tuple(k_pool.shape)} "
+                       f"table{tuple(block_table.shape)} seq_lens{tuple(seq_lens.shape)} "
+                       f"cu_seqlens_q{tuple(cu_seqlens_q.shape)}")
+    if any(t.stride(-1) != 1 for t in (x, k_pool, v_pool) if t.numel()):
+        raise PliError(f"{what}: a unit head_dim stride is required (the pools are used in place)")
+    return dev
+
+
+def attn_varlen_paged(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor,
+                      seq_lens: torch.Tensor, cu_seqlens_q: torch.Tensor, max_kv: int | None = None,
+                      scale: float | None = None, causal: bool = True,
+                      out: torch.Tensor | None = None) -> torch.Tensor:
+    """Attention of a packed, mixed batch straight over a paged pool: q
+    [max_tokens, Hq, D], sequence b owning rows cu_seqlens_q[b] ..
+    cu_seqlens_q[b+1] - 1 (any count, 0 included); k_pool / v_pool
+    [num_blocks, block_size, Hkv, D] views used in place; block_table int32
+    [B, max_blocks]; seq_lens int32 [B], each sequence's kv length with this
+    step's tokens already appended (clamped to max_kv, default max_blocks *
+    block_size).  causal masks bottom-right per sequence.  The three int32
+    tensors are read on the device (graph-replayable).  Returns [max_tokens, Hq,
+    D]; a row that sees no key is 0, rows past cu_seqlens_q[B] are not written."""
+    dev = _check_varlen("attn_varlen_paged", q, k_pool, v_pool, block_table, seq_lens, cu_seqlens_q)
+    T, H, D = q.shape
+    num_blocks, bs, Hkv, _ = k_pool.shape
+    B, max_blocks = block_table.shape
+    if Hkv == 0 or H % Hkv != 0:
+        raise PliError(f"heads {H} not a multiple of kv heads {Hkv}")
+    cap = max_blocks * bs
+    max_kv = cap if max_kv is None else int(max_kv)
+    if not 0 <= max_kv <= cap:
+        raise PliError(f"max_kv {max_kv} outside the table row [0, {cap}]")
+    if out is None:
+        out = torch.empty((T, H, D), device=q.device, dtype=q.dtype)
+    _require_gpu(q, out)
+    if tuple(out.shape) != (T, H, D) or (out.numel() and out.stride(-1) != 1):
+        raise PliError("bad output tensor")
+    if scale is None:
+        scale = D ** -0.5
+    st = (_c_i64 * 10)(*(int(x) for x in (q.stride(0), q.stride(1),
+                                          k_pool.stride(0), k_pool.stride(1), k_pool.stride(2),
+                                          v_pool.stride(0), v_pool.stride(1), v_pool.stride(2),
+                                          out.stride(0), out.stride(1))))
+    with _on_device(dev):
+        rc = lib().pli_attn_varlen_paged(_ptr(q), _ptr(k_pool), _ptr(v_pool), _ptr(out), _ptr(cu_seqlens_q),
+                                         _ptr(block_table), _ptr(seq_lens), B, T, H, Hkv, D, bs, num_blocks,
+                                         max_blocks, max_kv, st, float(scale), int(bool(causal)), _dtype_code(q),
+                                         _stream(dev))
+    _check(rc, "pli_attn_varlen_paged")
+    return out
+
+
+def kv_append_varlen_paged(k_new: torch.Tensor, v_new: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor,
+                           block_table: torch.Tensor, seq_lens: torch.Tensor, cu_seqlens_q: torch.Tensor) -> None:
+    """Write packed row cu_seqlens_q[b] + i of k_new / v_new [max_tokens, Hkv,
+    D] to logical position seq_lens[b] - q_len(b) + i of sequence b in the paged
+    pools (negative positions and positions past the table row are dropped):
+    seq_lens already counts the new tokens, so this call and attn_varlen_paged
+    take the same three device tensors."""
+    dev = _check_varlen("kv_append_varlen_paged", k_new, k_pool, v_pool, block_table, seq_lens, cu_seqlens_q)
+    _require_gpu(k_new, v_new)
+    T, Hkv, D = k_new.shape
+    if tuple(v_new.shape) != tuple(k_new.shape) or k_pool.shape[2] != Hkv or (v_new.numel() and v_new.stride(-1) != 1):
+        raise PliError(f"kv_append_varlen_paged shape mismatch new{tuple(k_new.shape)} v{tuple(v_new.shape)} "
+                       f"pool{tuple(k_pool.shape)}")
+    num_blocks, bs = k_pool.shape[0], k_pool.shape[1]
+    st = (_c_i64 * 10)(*(int(x) for x in (k_new.stride(0), k_new.stride(1),
+                                          k_pool.stride(0), k_pool.stride(1), k_pool.stride(2),
+                                          v_pool.stride(0), v_pool.stride(1), v_pool.stride(2),
+                                          v_new.stride(0), v_new.stride(1))))
+    with _on_device(dev):
+        rc = lib().pli_kv_append_varlen_paged(_ptr(k_new), _ptr(v_new), _ptr(k_pool), _ptr(v_pool),
+                                              _ptr(cu_seqlens_q), _ptr(block_table), _ptr(seq_lens),
+                                              block_table.shape[0], T, Hkv, D, bs, num_blocks, block_table.shape[1],
+                                              st, _dtype_code(k_new), _stream(dev))
+    _check(rc, "pli_kv_append_varlen_paged")
 
 
 # ---------------------------------------------------------------------- MoE
