@@ -470,6 +470,86 @@ int pli_kv_append_varlen_paged(const void* k_new, const void* v_new,
                                int max_blocks_per_seq, const int64_t* strides,
                                int dtype, void* stream);
 
+/* The same four calls over a 1-byte KV pool: OCP fp8 e4m3fn codes (not fnuz;
+ * 0x7E = 448 the largest finite value, 0x7F / 0xFF NaN, no infinity) in the
+ * layout above, one byte per element, so the same memory holds twice the
+ * tokens and decode attention reads half the bytes.
+ *
+ * Pools: k_pool / v_pool point at page 0 of byte pools; their strides are in
+ *   elements, which are bytes.
+ * Scales: k_scale / v_scale are device fp32 [kv_heads]; an element's value is
+ *   code * scale[kv head].  They are read on the device, so a captured call
+ *   replays while the scales change in place.  NULL means all ones.  A scale
+ *   must be finite and > 0; any other value gives unspecified values in that
+ *   head's rows and never an access outside an operand.
+ * Attention: scores = scale * k_scale[hk] * (q . K8), O = v_scale[hk] *
+ *   softmax(scores) . V8, K8 / V8 the codes' values.  Each code is widened
+ *   exactly to q's type on its way into the kernel (every e4m3 value is a bf16
+ *   and an fp16 value); k_scale is folded into the softmax constant and v_scale
+ *   into the final 1/l, so the result is attention over the dequantised pool
+ *   with the arithmetic of the 16-bit kernels.  `dtype` is q / o's.
+ * Append: code = e4m3fn_rne(clamp(x * inv, -448, 448)), inv = 1.0f / scale[h]
+ *   and the product in fp32, round to nearest even.  NaN stays NaN (0x7F /
+ *   0xFF by its sign), +-inf and everything past +-448 saturate to +-448.
+ *   `dtype` is the source's (fp32 / fp16 / bf16).
+ *
+ * pli_attn_decode_paged_fp8: pli_attn_decode_paged otherwise, workspace from
+ *   pli_attn_decode_paged_workspace_size.  The MFMA kernel
+ *   attn_decode_paged_fp8 takes what attn_decode_paged takes with the pool
+ *   strides multiples of 16 (bytes) and q / o strides multiples of 8; it loads
+ *   16 codes per lane and instruction.  pli_last_route:
+ *   "attn_decode_paged_fp8", "attn_decode_paged_fp8+attn_decode_paged_combine"
+ *   or "attn_decode_paged_generic_fp8" (fp32 q, any head_dim <= 256, any
+ *   block_size; it decodes with csrc/fp8_codec.h).
+ * pli_attn_varlen_paged_fp8: pli_attn_varlen_paged otherwise; the same rule
+ *   picks "attn_varlen_paged_fp8" or "attn_varlen_paged_generic_fp8".
+ * pli_kv_append_paged_fp8 / pli_kv_append_varlen_paged_fp8: positions, drops
+ *   and clamps of the 16-bit appends.  strides as there: the source's in its
+ *   elements, the pools' in bytes.  Rows of whole 8-element chunks: head_dim
+ *   and every stride a multiple of 8, 16-byte aligned operands.
+ *   pli_last_route: "kv_append_paged_fp8" / "kv_append_varlen_paged_fp8".
+ * Argument checks, PLI_EINVAL and empty calls as for the 16-bit calls. */
+int pli_attn_decode_paged_fp8(const void* q, const void* k_pool,
+                              const void* v_pool, void* o,
+                              const int32_t* block_table,
+                              const int32_t* seq_lens, const float* k_scale,
+                              const float* v_scale, int batch, int heads,
+                              int kv_heads, int n_q, int head_dim,
+                              int block_size, int num_blocks,
+                              int max_blocks_per_seq, int max_kv,
+                              const int64_t* strides, float scale, int causal,
+                              int n_kv_add, void* workspace,
+                              size_t workspace_bytes, int dtype, void* stream);
+int pli_kv_append_paged_fp8(const void* k_new, const void* v_new, void* k_pool,
+                            void* v_pool, const int32_t* block_table,
+                            const int32_t* seq_lens, const float* k_scale,
+                            const float* v_scale, int batch, int n_new,
+                            int kv_heads, int head_dim, int block_size,
+                            int num_blocks, int max_blocks_per_seq,
+                            const int64_t* strides, int dtype, void* stream);
+int pli_attn_varlen_paged_fp8(const void* q, const void* k_pool,
+                              const void* v_pool, void* o,
+                              const int32_t* cu_seqlens_q,
+                              const int32_t* block_table,
+                              const int32_t* seq_lens, const float* k_scale,
+                              const float* v_scale, int batch, int max_tokens,
+                              int heads, int kv_heads, int head_dim,
+                              int block_size, int num_blocks,
+                              int max_blocks_per_seq, int max_kv,
+                              const int64_t* strides, float scale, int causal,
+                              int dtype, void* stream);
+int pli_kv_append_varlen_paged_fp8(const void* k_new, const void* v_new,
+                                   void* k_pool, void* v_pool,
+                                   const int32_t* cu_seqlens_q,
+                                   const int32_t* block_table,
+                                   const int32_t* seq_lens,
+                                   const float* k_scale, const float* v_scale,
+                                   int batch, int max_tokens, int kv_heads,
+                                   int head_dim, int block_size,
+                                   int num_blocks, int max_blocks_per_seq,
+                                   const int64_t* strides, int dtype,
+                                   void* stream);
+
 /* ------------------------------------------------------------------------
  * Tuning section: the same operations with an explicit kernel choice, for
  * A/B runs (tools/tune.py) and the per-variant parity tests.  Not part of

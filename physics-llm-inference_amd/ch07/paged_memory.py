@@ -25,6 +25,12 @@ attended over in place, through ``pli_kv_append_paged`` and
   ``pli_attn_varlen_paged`` (csrc/varlen_attn.hip), one launch each.
 
 No page is gathered into a contiguous tensor on the way.
+
+``PagedKVCache(..., kv_dtype=torch.float8_e4m3fn)`` keeps the pools as 1-byte
+OCP fp8 e4m3 codes with one fp32 scale per (layer, kv head) for K and for V
+(``k_scale`` / ``v_scale``, ones until ``set_scales``): the same four methods
+then quantise on append and attend through the ``*_fp8`` entry points, and the
+same memory holds twice the tokens.
 """
 from __future__ import annotations
 
@@ -45,9 +51,29 @@ class BlockTable:
         return len(self.block_indices)
 
 
-class PagedKVCache:
+class _CacheOptions(type):
+    """Construction options the reference's constructor does not have.
+    ``PagedKVCache.__init__`` keeps the reference's parameter list exactly
+    (tests/test_ch07_packed_cpu.py pins it), so the trailing keyword
+    ``kv_dtype`` of ``PagedKVCache(..., kv_dtype=...)`` is taken here, at the
+    call of the class, and is on the instance before ``__init__`` runs."""
+
+    def __call__(cls, *args, kv_dtype: torch.dtype | None = None, **kwargs):
+        if kv_dtype not in (None, torch.float8_e4m3fn):
+            raise ValueError(f"kv_dtype must be None or torch.float8_e4m3fn, got {kv_dtype}")
+        self = cls.__new__(cls)
+        self.kv_dtype = kv_dtype
+        self.__init__(*args, **kwargs)
+        return self
+
+
+class PagedKVCache(metaclass=_CacheOptions):
+    # None: the pools hold `dtype`; torch.float8_e4m3fn: 1-byte codes, `dtype` is q's (keyword of the class call)
+    kv_dtype: torch.dtype | None = None
+
     def __init__(self, num_blocks: int, block_size: int, num_layers: int, num_heads: int, head_dim: int,
                  dtype: torch.dtype = torch.float16, device: str = "cuda"):
+        kv_dtype = self.kv_dtype
         self.num_blocks = num_blocks
         self.block_size = block_size
         self.num_layers = num_layers
@@ -61,10 +87,16 @@ class PagedKVCache:
 
         # the pools exist only on a device (None otherwise, as in the reference)
         self.k_cache = self.v_cache = None
-        if torch.cuda.is_available() and torch.device(device).type == "cuda":
+        on_device = torch.cuda.is_available() and torch.device(device).type == "cuda"
+        if on_device:
             shape = (num_blocks, num_layers, block_size, num_heads, head_dim)
-            self.k_cache = torch.zeros(shape, dtype=dtype, device=device)
-            self.v_cache = torch.zeros(shape, dtype=dtype, device=device)
+            self.k_cache = torch.zeros(shape, dtype=kv_dtype or dtype, device=device)
+            self.v_cache = torch.zeros(shape, dtype=kv_dtype or dtype, device=device)
+        # fp8 pools: value = code * scale[layer, kv head]; the scales live where the pools do (host copies off-device)
+        self.k_scale = self.v_scale = None
+        if kv_dtype is not None:
+            self.k_scale = torch.ones(num_layers, num_heads, dtype=torch.float32, device=device if on_device else "cpu")
+            self.v_scale = torch.ones_like(self.k_scale)
 
     # ------------------------------------------------------------ allocator --
     def _blocks_for(self, num_tokens: int) -> int:
@@ -104,8 +136,9 @@ class PagedKVCache:
     def get_memory_usage(self) -> dict:
         free = len(self.free_blocks)
         used = self.num_blocks - free
-        # K and V, every layer, 2 bytes per element (the reference's fp16 figure)
-        bytes_per_block = 2 * self.num_layers * self.block_size * self.num_heads * self.head_dim * 2
+        # K and V, every layer, 2 bytes per element (the reference's fp16 figure), 1 for an fp8 cache
+        elem_bytes = 2 if self.kv_dtype is None else 1
+        bytes_per_block = 2 * self.num_layers * self.block_size * self.num_heads * self.head_dim * elem_bytes
         mb = 1024 * 1024
         return {
             "total_blocks": self.num_blocks,
@@ -126,6 +159,24 @@ class PagedKVCache:
             raise IndexError(f"layer {layer} outside [0, {self.num_layers})")
         # [num_blocks, block_size, heads, head_dim] views: the layer is in the page stride
         return self.k_cache[:, layer], self.v_cache[:, layer]
+
+    def set_scales(self, layer: int, k_scale, v_scale) -> None:
+        """Set an fp8 cache's per-kv-head scales of one layer, in place (so a
+        captured graph sees them): each a tensor or sequence of num_heads
+        finite values > 0.  Tokens already in the pool keep the codes they were
+        stored with."""
+        if self.kv_dtype is None:
+            raise ValueError("set_scales needs an fp8 cache (kv_dtype=torch.float8_e4m3fn)")
+        if not 0 <= layer < self.num_layers:
+            raise IndexError(f"layer {layer} outside [0, {self.num_layers})")
+        new = [torch.as_tensor(s, dtype=torch.float32).detach().cpu() for s in (k_scale, v_scale)]
+        for name, t in zip(("k_scale", "v_scale"), new):
+            if tuple(t.shape) != (self.num_heads,):
+                raise ValueError(f"{name} needs shape ({self.num_heads},), got {tuple(t.shape)}")
+            if not bool((torch.isfinite(t) & (t > 0)).all()):
+                raise ValueError(f"{name} must be finite and > 0")
+        self.k_scale[layer].copy_(new[0])
+        self.v_scale[layer].copy_(new[1])
 
     def tables(self, request_ids, max_blocks: int | None = None):
         """(block_table int32 [B, max_blocks], seq_lens int32 [B]) of the given
@@ -153,6 +204,10 @@ class PagedKVCache:
         count the new tokens."""
         k_pool, v_pool = self._pools(layer)
         start = seq_lens - k_new.shape[1]
+        if self.kv_dtype is not None:
+            pli_hip.kv_append_paged_fp8(k_new, v_new, k_pool, v_pool, block_table, start, self.k_scale[layer],
+                                        self.v_scale[layer])
+            return
         pli_hip.kv_append_paged(k_new, v_new, k_pool, v_pool, block_table, start)
 
     def attend(self, layer: int, q: torch.Tensor, block_table: torch.Tensor, seq_lens: torch.Tensor,
@@ -161,6 +216,9 @@ class PagedKVCache:
         seq_lens[b] + n_kv_add tokens of this layer's pages, read in place;
         causal masks bottom-right per sequence.  Returns [B, Sq, Hq, head_dim]."""
         k_pool, v_pool = self._pools(layer)
+        if self.kv_dtype is not None:
+            return pli_hip.attn_decode_paged_fp8(q, k_pool, v_pool, block_table, seq_lens, self.k_scale[layer],
+                                                 self.v_scale[layer], causal=causal, n_kv_add=n_kv_add)
         return pli_hip.attn_decode_paged(q, k_pool, v_pool, block_table, seq_lens, causal=causal,
                                          n_kv_add=n_kv_add)
 
@@ -186,6 +244,10 @@ class PagedKVCache:
         tokens of their sequences: row cu[b] + i goes to position
         seq_lens[b] - (cu[b+1] - cu[b]) + i."""
         k_pool, v_pool = self._pools(layer)
+        if self.kv_dtype is not None:
+            pli_hip.kv_append_varlen_paged_fp8(k_new, v_new, k_pool, v_pool, block_table, seq_lens, cu_seqlens_q,
+                                               self.k_scale[layer], self.v_scale[layer])
+            return
         pli_hip.kv_append_varlen_paged(k_new, v_new, k_pool, v_pool, block_table, seq_lens, cu_seqlens_q)
 
     def attend_packed(self, layer: int, q: torch.Tensor, block_table: torch.Tensor, seq_lens: torch.Tensor,
@@ -195,6 +257,9 @@ class PagedKVCache:
         mixed; causal masks bottom-right per sequence.  Returns [tokens, Hq,
         head_dim]."""
         k_pool, v_pool = self._pools(layer)
+        if self.kv_dtype is not None:
+            return pli_hip.attn_varlen_paged_fp8(q, k_pool, v_pool, block_table, seq_lens, cu_seqlens_q,
+                                                 self.k_scale[layer], self.v_scale[layer], causal=causal)
         return pli_hip.attn_varlen_paged(q, k_pool, v_pool, block_table, seq_lens, cu_seqlens_q, causal=causal)
 
 
@@ -229,6 +294,15 @@ Mixed steps (prompt chunks and decode rows in one launch):
     a tile; the four waves of a workgroup share each 32-key K/V image, loaded
     once through the block table, and a tile stops at its last row's causal
     limit.  tables_packed / append_packed / attend_packed drive it.
+
+A 1-byte cache (kv_dtype=torch.float8_e4m3fn):
+  - The pools hold OCP fp8 e4m3 codes, value = code * scale[layer, kv head];
+    the same HBM holds twice the tokens and decode reads half the bytes.
+  - The appends quantise (x / scale, clamped to +-448, round to nearest even);
+    the attention kernels widen each code exactly to q's type between the
+    global load and the LDS write, so the MFMA loop and the softmax are those of
+    the 16-bit kernels, with k_scale folded into the softmax constant and
+    v_scale into the final 1/l.
 """
 
 

@@ -119,6 +119,19 @@ inline bool paged_fast_path(int dtype, int head_dim, int64_t rows_per_kv_head, i
         if (strides12[i] % 8 != 0) return false;
     return aligned16_operands;
 }
+// The same rule for a 1-byte (fp8 e4m3) pool, attn_decode_paged_fp8: dtype is
+// q / o's, whose strides stay multiples of 8 elements; a pool row is loaded
+// in 16-byte chunks of 16 codes, so the pool strides (in elements = bytes) are
+// multiples of 16.
+inline bool paged_fast_path_fp8(int dtype, int head_dim, int64_t rows_per_kv_head, int block_size, float scale,
+                                const int64_t* strides12, bool aligned16_operands) {
+    int64_t qo[12];
+    for (int i = 0; i < 12; ++i) qo[i] = (i >= 3 && i < 9) ? 0 : strides12[i];
+    if (!paged_fast_path(dtype, head_dim, rows_per_kv_head, block_size, scale, qo, aligned16_operands)) return false;
+    for (int i = 3; i < 9; ++i)
+        if (strides12[i] % 16 != 0) return false;
+    return true;
+}
 
 // ---- split-K plan -----------------------------------------------------------
 // The grid and the workspace are sized for max_kv, a host upper bound on every

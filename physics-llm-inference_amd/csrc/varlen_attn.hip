@@ -37,8 +37,12 @@
 // modelled on attn_decode_paged_generic -- a correctness path, not tuned.
 // kv_append_varlen_paged_kernel: one thread per 16-byte chunk of a packed
 // token's K and V row.
+// attn_varlen_paged_fp8 / attn_varlen_paged_generic_fp8 /
+// kv_append_varlen_paged_fp8 are the same three over 1-byte pools of fp8 e4m3
+// codes (below, "1-byte pools"); the 16-bit kernels are not touched by them.
 #include <cmath>
 
+#include "fp8_kv.h"
 #include "pli_common.h"
 #include "varlen_plan.h"
 
@@ -376,6 +380,278 @@ __global__ __launch_bounds__(256) void kv_append_varlen_paged_kernel(
     *reinterpret_cast<i32x4*>(vd) = *reinterpret_cast<const i32x4*>(vs);
 }
 
+// ---- 1-byte pools: OCP fp8 e4m3fn codes, value = code * scale[kv head] --------
+// attn_varlen_paged_fp8<T, D> is attn_varlen_paged<T, D> with the pools read as
+// bytes.  A thread loads D/8 codes (16 bytes for D 128, 8 for D 64) of one row,
+// so the 256 threads cover a 32-key step of K and of V in ONE pass each (the
+// 16-bit kernel takes two at D 128): 8 threads per row, wave w the rows 8w ..
+// 8w + 7, which lie in 16-key group w / 2.  The codes are widened (exactly, by
+// v_cvt_scalef32_pk_*_fp8) to T between the register stage and the LDS write;
+// the image, the MFMA loop and the softmax are those of the 16-bit kernel.
+// k_scale[hk] is folded into the softmax constant, v_scale[hk] into the final
+// 1/l.  Pool strides are in bytes; the scales are read on the device.
+template <typename T, int D>
+__global__ __launch_bounds__(256, 2) void attn_varlen_paged_fp8(
+    const uint16_t* __restrict__ q, const uint8_t* __restrict__ k, const uint8_t* __restrict__ v,
+    uint16_t* __restrict__ o, const int32_t* __restrict__ cu, const int32_t* __restrict__ table,
+    const int32_t* __restrict__ seq_lens, const float* __restrict__ k_scale, const float* __restrict__ v_scale,
+    int batch, int max_tokens, int Hkv, int G, VarStrides st, PagedTable tb, float c_in, int causal, int max_kv,
+    int tiles_upper) {
+    using L = VarLayout<D>;
+    using Stage = typename std::conditional<D == 128, i32x4, i32x2>::type;  // D/8 codes
+    constexpr int KSTEPS = D / 32;  // 32-d k-steps of K.Q^T
+    constexpr int DB = D / 16;      // 16-d blocks of O
+    __shared__ __attribute__((aligned(16))) char smem[L::LDS];
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l16 = lane & 15, g = lane >> 4;
+    const int hk = blockIdx.x % Hkv;
+    const int w = blockIdx.x / Hkv;
+    const int tpt = VAR_BM / G;
+    const VarTile found = find_tile_wave(cu, batch, tpt, tiles_upper, w, lane);
+    const int b = __builtin_amdgcn_readfirstlane(found.b);
+    if (b < 0) return;  // every wave finds the same answer: the whole workgroup leaves
+    const int tile = __builtin_amdgcn_readfirstlane(found.tile);
+    const int cu_b = cu[b];
+    const int q_len = varlen_q_len(cu_b, cu[b + 1]);
+    const int live = varlen_tokens_live(cu[batch], max_tokens);
+    const int Nk = varlen_n_kv(seq_lens[b], max_kv);
+    const int key_end = varlen_key_end(Nk, q_len, tile, tpt, causal);
+    const int nsteps = cdiv(key_end, VAR_STEP);
+    const float c = c_in * fp8_scale_of(k_scale, hk);
+    const float vsc = fp8_scale_of(v_scale, hk);
+
+    const int r = wave * VAR_ROWS + l16;
+    const int64_t qi = (int64_t)tile * tpt + r / G;
+    const int hq = hk * G + r % G;
+    const bool row_ok = qi < q_len;
+    const bool wave_on = __builtin_amdgcn_readfirstlane((int64_t)tile * tpt + (wave * VAR_ROWS) / G < q_len ? 1 : 0) != 0;
+    const int tok = varlen_token(cu_b, qi, max_tokens);
+    i32x4 qf[KSTEPS];
+    {
+        const uint16_t* src = q + (int64_t)tok * st.qt + (int64_t)hq * st.qh + 8 * g;
+#pragma unroll
+        for (int ks = 0; ks < KSTEPS; ++ks) {
+            const i32x4 x = *reinterpret_cast<const i32x4*>(src + 32 * ks);
+            qf[ks] = row_ok ? x : i32x4{0, 0, 0, 0};
+        }
+    }
+    const int hi = row_ok ? varlen_row_limit(Nk, q_len, (int)qi, causal) : -1;
+
+    // cooperative row-major loads: thread loads chunk rch (D/8 codes) of step row rrow
+    constexpr int CPR = 8, LB = D / 8;
+    static_assert(256 / CPR == VAR_STEP, "one pass covers a step");
+    const int rrow = tid / CPR, rch = tid % CPR;
+    const uint8_t* kp = k + LB * rch;
+    const uint8_t* vp = v + LB * rch;
+    auto ld = [](const uint8_t* p) { return *reinterpret_cast<const Stage*>(p); };
+    // raw table entry of the wave's 16-key group: clamping here would wait for the load at once
+    auto page = [&](int key0) {
+        return table[paged_table_index(b, varlen_group_block(key0, (wave * (64 / CPR)) / 16, Nk, tb), tb)];
+    };
+    auto load_step = [&](int key0, int e, Stage& kr, Stage& vr) {
+        const int key = varlen_load_key(key0, rrow, Nk);
+        kr = ld(kp + varlen_kv_offset(e, key, hk, tb, st.k));
+        vr = ld(vp + varlen_kv_offset(e, key, hk, tb, st.v));
+    };
+    const int kw = rrow * L::KS + rch * 2 * LB;                 // D/8 T = 2 LB bytes per thread
+    const int vw = rrow * L::VS + rch * 2 * LB;
+    // the conversion point: codes -> T, then the row-major padded image
+    auto store_step = [&](char* img, const Stage& kr, const Stage& vr) {
+        if constexpr (D == 128) {
+            i32x4 lo, hi4;
+            fp8_widen16<T>(vr, lo, hi4);
+            lds_write_b128(img + L::KBYTES, vw, lo);
+            lds_write_b128(img + L::KBYTES, vw + 16, hi4);
+            fp8_widen16<T>(kr, lo, hi4);
+            lds_write_b128(img, kw, lo);
+            lds_write_b128(img, kw + 16, hi4);
+        } else {
+            lds_write_b128(img + L::KBYTES, vw, fp8_widen8<T>(vr));
+            lds_write_b128(img, kw, fp8_widen8<T>(kr));
+        }
+    };
+    const int kr_off = l16 * L::KS + g * 16;                    // K fragment read
+    const int qq = l16 >> 2, pp = lane & 3;
+    const int vr_off = (4 * g + qq) * L::VS + 8 * pp;           // tr read: key 4g+qq, col 4pp
+
+    f32x4 oacc[DB];
+#pragma unroll
+    for (int d = 0; d < DB; ++d) oacc[d] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float m_run = -1e30f, l_run = 0.f;
+
+    auto compute = [&](const char* img, int key0) {
+        const char* kt = img;
+        const char* vt = img + L::KBYTES;
+        f32x4 s[2];
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) {
+            s[kb] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < KSTEPS; ++ks) {
+                const i32x4 kf = lds_read_b128(kt, kr_off + 16 * kb * L::KS + 64 * ks);
+                s[kb] = mfma16x16x32<T>(kf, qf[ks], s[kb]);
+            }
+        }
+        if (key0 + VAR_STEP - 1 > hi) {
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                for (int rr = 0; rr < 4; ++rr)
+                    if (key0 + 16 * kb + 4 * g + rr > hi) s[kb][rr] = -INFINITY;
+        }
+        float mx = max3(s[0][0], s[0][1], s[0][2]);
+        mx = max3(mx, s[0][3], s[1][0]);
+        mx = max3(mx, s[1][1], s[1][2]);
+        mx = fmaxf(mx, s[1][3]);
+        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        const float m_new = fmaxf(m_run, mx * c);
+        const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+        m_run = m_new;
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) s[kb][rr] = __builtin_amdgcn_exp2f(fmaf(s[kb][rr], c, -m_new));
+        const uint32_t p0 = pack2<T>(s[0][0], s[0][1]), p1 = pack2<T>(s[0][2], s[0][3]);
+        const uint32_t p2 = pack2<T>(s[1][0], s[1][1]), p3 = pack2<T>(s[1][2], s[1][3]);
+        const i32x4 pb = {(int)p0, (int)p1, (int)p2, (int)p3};
+        l_run = fmaf(l_run, alpha, add_pair<T>(p0, add_pair<T>(p1, add_pair<T>(p2, add_pair<T>(p3, 0.f)))));
+#pragma unroll
+        for (int d = 0; d < DB; ++d) {
+            const i32x2 lo = lds_read_tr16(vt, vr_off + 32 * d);
+            const i32x2 hi2 = lds_read_tr16(vt, vr_off + 32 * d + 16 * L::VS);
+            oacc[d] = mfma16x16x32<T>(i32x4{lo.x, lo.y, hi2.x, hi2.y}, pb, oacc[d] * alpha);
+        }
+    };
+
+    // the pipeline of attn_varlen_paged: loads two steps ahead in two register
+    // stages, entries three steps ahead, one barrier per step; the loads and LDS
+    // writes of steps past the last one are not skipped (their addresses are
+    // clamped like any other), see the comment there
+    Stage ka, va, kb2, vb2;
+    int pn = 0;
+    auto body = [&](int t, int cur, Stage& kfree, Stage& vfree, Stage& knext, Stage& vnext) {
+        const int pf = page((t + 3) * VAR_STEP);
+        load_step((t + 2) * VAR_STEP, pn, kfree, vfree);
+        pn = pf;
+        if (wave_on && t < nsteps) compute(smem + cur * L::IMAGE, t * VAR_STEP);
+        store_step(smem + (cur ^ 1) * L::IMAGE, knext, vnext);
+        __syncthreads();
+    };
+    if (nsteps > 0) {
+        const int p0 = page(0), p1 = page(VAR_STEP);
+        pn = page(2 * VAR_STEP);
+        load_step(0, p0, ka, va);
+        load_step(VAR_STEP, p1, kb2, vb2);
+        store_step(smem, ka, va);
+        __syncthreads();
+    }
+    for (int t = 0; t < nsteps; t += 2) {
+        body(t, 0, ka, va, kb2, vb2);
+        body(t + 1, 1, kb2, vb2, ka, va);
+    }
+
+    l_run += __shfl_xor(l_run, 16, 64);
+    l_run += __shfl_xor(l_run, 32, 64);
+    if (!varlen_row_stored(cu_b, qi, q_len, live)) return;
+    const float inv = l_run > 0.f ? vsc / l_run : 0.f;
+    uint16_t* op = o + (int64_t)tok * st.ot + (int64_t)hq * st.oh + 4 * g;
+#pragma unroll
+    for (int d = 0; d < DB; ++d)
+        *reinterpret_cast<i32x2*>(op + 16 * d) = i32x2{(int)pack2<T>(oacc[d][0] * inv, oacc[d][1] * inv),
+                                                        (int)pack2<T>(oacc[d][2] * inv, oacc[d][3] * inv)};
+}
+
+// attn_varlen_paged_generic over 1-byte pools: T is q / o's type, every code
+// goes through fp8_e4m3_decode (fp8_codec.h).  Correctness path only.
+template <typename T>
+__global__ __launch_bounds__(64) void attn_varlen_paged_generic_fp8(
+    const T* __restrict__ q, const uint8_t* __restrict__ k, const uint8_t* __restrict__ v, T* __restrict__ o,
+    const int32_t* __restrict__ cu, const int32_t* __restrict__ table, const int32_t* __restrict__ seq_lens,
+    const float* __restrict__ k_scale, const float* __restrict__ v_scale, int batch, int max_tokens, int H, int G,
+    int D, VarStrides st, PagedTable tb, float scale, int causal, int max_kv) {
+    const int lane = threadIdx.x;
+    const int h = blockIdx.x % H;
+    const int t = blockIdx.x / H;
+    if (t >= varlen_tokens_live(cu[batch], max_tokens)) return;
+    const int b = varlen_owner(cu, batch, t);
+    if (b < 0) return;
+    const int hk = h / G;
+    const int q_len = varlen_q_len(cu[b], cu[b + 1]);
+    const int Nk = varlen_n_kv(seq_lens[b], max_kv);
+    const int nvis = varlen_row_limit(Nk, q_len, t - cu[b], causal) + 1;
+    const float sc = scale * fp8_scale_of(k_scale, hk);
+    const T* qrow = q + (int64_t)t * st.qt + (int64_t)h * st.qh;
+    float qv[VGEN_DPL], acc[VGEN_DPL];
+#pragma unroll
+    for (int i = 0; i < VGEN_DPL; ++i) {
+        const int d = lane + 64 * i;
+        qv[i] = d < D ? elem<T>::to_f32(qrow[d]) : 0.f;
+        acc[i] = 0.f;
+    }
+    float m = -INFINITY, l = 0.f;
+    for (int j = 0; j < nvis; ++j) {
+        const uint8_t* krow = k + paged_key_offset(table, b, j, hk, tb, st.k);
+        const uint8_t* vrow = v + paged_key_offset(table, b, j, hk, tb, st.v);
+        float dot = 0.f;
+#pragma unroll
+        for (int i = 0; i < VGEN_DPL; ++i) {
+            const int d = lane + 64 * i;
+            if (d < D) dot = fmaf(qv[i], fp8_e4m3_decode(krow[d]), dot);
+        }
+        const float s = wave_sum(dot) * sc;
+        const float m_new = fmaxf(m, s);
+        const float a = __expf(m - m_new), p = __expf(s - m_new);
+        l = fmaf(l, a, p);
+#pragma unroll
+        for (int i = 0; i < VGEN_DPL; ++i) {
+            const int d = lane + 64 * i;
+            if (d < D) acc[i] = fmaf(acc[i], a, p * fp8_e4m3_decode(vrow[d]));
+        }
+        m = m_new;
+    }
+    const float inv = l > 0.f ? fp8_scale_of(v_scale, hk) / l : 0.f;  // no visible key: O = 0
+    T* orow = o + (int64_t)t * st.ot + (int64_t)h * st.oh;
+#pragma unroll
+    for (int i = 0; i < VGEN_DPL; ++i) {
+        const int d = lane + 64 * i;
+        if (d < D) orow[d] = elem<T>::from_f32(acc[i] * inv);
+    }
+}
+
+// kv_append_varlen_paged_kernel that quantises: one thread per 8 elements of a
+// packed token's row, read as 16 (bf16 / fp16) or 32 (fp32) bytes of the source
+// and stored as one 8-byte chunk of codes (fp8_kv.h).  Source strides in bytes
+// of the source, pool strides in bytes.
+template <typename T>
+__global__ __launch_bounds__(256) void kv_append_varlen_paged_fp8(
+    const char* __restrict__ kn, const char* __restrict__ vn, char* __restrict__ kpool,
+    char* __restrict__ vpool, const int32_t* __restrict__ cu, const int32_t* __restrict__ table,
+    const int32_t* __restrict__ seq_lens, const float* __restrict__ k_scale, const float* __restrict__ v_scale,
+    int batch, int max_tokens, int Hkv, int cpr, VarAppendStrides st, PagedTable tb) {
+    const int64_t total = (int64_t)max_tokens * Hkv * cpr;
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int ch = idx % cpr;
+    const int h = (idx / cpr) % Hkv;
+    const int t = (int)(idx / ((int64_t)cpr * Hkv));
+    if (t >= varlen_tokens_live(cu[batch], max_tokens)) return;
+    const int b = varlen_owner(cu, batch, t);
+    if (b < 0) return;
+    const int64_t pos = varlen_append_pos(seq_lens[b], varlen_q_len(cu[b], cu[b + 1]), t - cu[b],
+                                          (int64_t)tb.max_blocks_per_seq * tb.block_size);
+    if (pos < 0) return;
+    constexpr int SRC = 8 * elem<T>::bytes;
+    const char* ks = kn + (int64_t)t * st.kt + (int64_t)h * st.kh + SRC * ch;
+    const char* vs = vn + (int64_t)t * st.vt + (int64_t)h * st.vh + SRC * ch;
+    char* kd = kpool + paged_key_offset(table, b, (int)pos, h, tb, st.k) + 8 * ch;
+    char* vd = vpool + paged_key_offset(table, b, (int)pos, h, tb, st.v) + 8 * ch;
+    *reinterpret_cast<i32x2*>(kd) = fp8_encode8<T>(ks, 1.0f / fp8_scale_of(k_scale, h));
+    *reinterpret_cast<i32x2*>(vd) = fp8_encode8<T>(vs, 1.0f / fp8_scale_of(v_scale, h));
+}
+
 struct VarCall {
     const void *q, *k, *v;
     void* o;
@@ -403,6 +679,36 @@ int launch_varlen_generic(const VarCall& a) {
                        (const T*)a.q, (const T*)a.k, (const T*)a.v, (T*)a.o, a.cu, a.table, a.seq_lens, a.B, a.T,
                        a.H, a.H / a.Hkv, a.D, a.st, a.tb, a.scale, a.causal, a.max_kv);
     return launch_status("attn_varlen_paged_generic");
+}
+
+template <typename T, int D>
+int launch_varlen_fp8(const VarCall& a, const Fp8Scales& sc, int64_t tiles_upper) {
+    const float c = a.scale * 1.4426950408889634f;
+    hipLaunchKernelGGL((attn_varlen_paged_fp8<T, D>), dim3((unsigned)(tiles_upper * a.Hkv)), dim3(256), 0, a.stream,
+                       (const uint16_t*)a.q, (const uint8_t*)a.k, (const uint8_t*)a.v, (uint16_t*)a.o, a.cu, a.table,
+                       a.seq_lens, sc.k, sc.v, a.B, a.T, a.Hkv, a.H / a.Hkv, a.st, a.tb, c, a.causal, a.max_kv,
+                       (int)tiles_upper);
+    return launch_status("attn_varlen_paged_fp8");
+}
+
+template <typename T>
+int launch_varlen_generic_fp8(const VarCall& a, const Fp8Scales& sc) {
+    hipLaunchKernelGGL((attn_varlen_paged_generic_fp8<T>), dim3((unsigned)((int64_t)a.T * a.H)), dim3(64), 0,
+                       a.stream, (const T*)a.q, (const uint8_t*)a.k, (const uint8_t*)a.v, (T*)a.o, a.cu, a.table,
+                       a.seq_lens, sc.k, sc.v, a.B, a.T, a.H, a.H / a.Hkv, a.D, a.st, a.tb, a.scale, a.causal,
+                       a.max_kv);
+    return launch_status("attn_varlen_paged_generic_fp8");
+}
+
+template <typename T>
+int launch_varlen_append_fp8(const char* kn, const char* vn, char* kpool, char* vpool, const int32_t* cu,
+                             const int32_t* table, const int32_t* seq_lens, const Fp8Scales& sc, int batch,
+                             int max_tokens, int Hkv, int cpr, const VarAppendStrides& st, const PagedTable& tb,
+                             hipStream_t stream) {
+    const int64_t total = (int64_t)max_tokens * Hkv * cpr;
+    hipLaunchKernelGGL(kv_append_varlen_paged_fp8<T>, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, stream, kn,
+                       vn, kpool, vpool, cu, table, seq_lens, sc.k, sc.v, batch, max_tokens, Hkv, cpr, st, tb);
+    return launch_status("kv_append_varlen_paged_fp8");
 }
 
 }  // namespace
@@ -507,4 +813,116 @@ extern "C" int pli_kv_append_varlen_paged(const void* k_new, const void* v_new, 
                        cu_seqlens_q, block_table, seq_lens, batch, max_tokens, kv_heads, cpr, st,
                        paged_table(block_size, num_blocks, max_blocks_per_seq));
     return launch_status("kv_append_varlen_paged");
+}
+
+extern "C" int pli_attn_varlen_paged_fp8(const void* q, const void* k_pool, const void* v_pool, void* o,
+                                         const int32_t* cu_seqlens_q, const int32_t* block_table,
+                                         const int32_t* seq_lens, const float* k_scale, const float* v_scale,
+                                         int batch, int max_tokens, int heads, int kv_heads, int head_dim,
+                                         int block_size, int num_blocks, int max_blocks_per_seq, int max_kv,
+                                         const int64_t* strides, float scale, int causal, int dtype, void* stream) {
+    using namespace pli;
+    clear_error();
+    PLI_REQUIRE(batch >= 0 && max_tokens >= 0 && heads > 0 && kv_heads > 0 && head_dim > 0 && num_blocks >= 0 &&
+                    max_blocks_per_seq >= 0 && max_kv >= 0,
+                "pli_attn_varlen_paged_fp8: bad shape B=%d tokens=%d H=%d Hkv=%d D=%d blocks=%d "
+                "max_blocks_per_seq=%d max_kv=%d",
+                batch, max_tokens, heads, kv_heads, head_dim, num_blocks, max_blocks_per_seq, max_kv);
+    PLI_REQUIRE(heads % kv_heads == 0, "pli_attn_varlen_paged_fp8: heads %d not a multiple of kv_heads %d", heads,
+                kv_heads);
+    PLI_REQUIRE(dtype == PLI_F32 || dtype == PLI_F16 || dtype == PLI_BF16,
+                "pli_attn_varlen_paged_fp8: bad dtype %d", dtype);
+    PLI_REQUIRE(std::isfinite(scale), "pli_attn_varlen_paged_fp8: non-finite scale");
+    PLI_REQUIRE(block_size > 0, "pli_attn_varlen_paged_fp8: block_size %d must be positive", block_size);
+    PLI_REQUIRE((int64_t)max_kv <= (int64_t)max_blocks_per_seq * block_size,
+                "pli_attn_varlen_paged_fp8: max_kv %d past the table row (%d blocks of %d tokens)", max_kv,
+                max_blocks_per_seq, block_size);
+    PLI_REQUIRE((int64_t)max_blocks_per_seq * block_size < (1ll << 31),
+                "pli_attn_varlen_paged_fp8: a table row of %d blocks x %d tokens passes 2^31 keys",
+                max_blocks_per_seq, block_size);
+    // no output rows: the (possibly NULL, pli.h) operands are not read
+    if (batch == 0 || max_tokens == 0) return PLI_OK;
+    PLI_REQUIRE(q && o && k_pool && v_pool && cu_seqlens_q && block_table && seq_lens && strides,
+                "pli_attn_varlen_paged_fp8: null pointer");
+    PLI_REQUIRE(num_blocks > 0 && max_blocks_per_seq > 0,
+                "pli_attn_varlen_paged_fp8: empty pool or table (blocks=%d max_blocks_per_seq=%d)", num_blocks,
+                max_blocks_per_seq);
+    VarCall a;
+    a.q = q, a.k = k_pool, a.v = v_pool, a.o = o, a.cu = cu_seqlens_q, a.table = block_table, a.seq_lens = seq_lens;
+    a.B = batch, a.T = max_tokens, a.H = heads, a.Hkv = kv_heads, a.D = head_dim, a.max_kv = max_kv;
+    a.causal = causal != 0, a.scale = scale, a.stream = (hipStream_t)stream;
+    // strides[10] as for pli_attn_varlen_paged; the pool strides count 1-byte elements
+    a.st = VarStrides{strides[0], strides[1], strides[8], strides[9], PagedPool{strides[2], strides[3], strides[4]},
+                      PagedPool{strides[5], strides[6], strides[7]}};
+    a.tb = paged_table(block_size, num_blocks, max_blocks_per_seq);
+    const Fp8Scales sc{k_scale, v_scale};
+    const bool fast = varlen_fast_path_fp8(dtype, head_dim, heads, kv_heads, block_size, scale, strides,
+                                           aligned16(q) && aligned16(k_pool) && aligned16(v_pool) && aligned16(o));
+    if (!fast) {
+        PLI_REQUIRE(head_dim <= VGEN_MAXD, "pli_attn_varlen_paged_fp8: head_dim %d > %d", head_dim, VGEN_MAXD);
+        PLI_REQUIRE((int64_t)max_tokens * heads < (1ll << 31), "pli_attn_varlen_paged_fp8: grid too large");
+        if (dtype == PLI_F32) return launch_varlen_generic_fp8<float>(a, sc);
+        return dtype == PLI_BF16 ? launch_varlen_generic_fp8<bf16_t>(a, sc) : launch_varlen_generic_fp8<f16_t>(a, sc);
+    }
+    const int64_t tiles_upper = varlen_tiles_upper(max_tokens, heads / kv_heads, batch);
+    PLI_REQUIRE(tiles_upper * kv_heads < (1ll << 31), "pli_attn_varlen_paged_fp8: grid too large");
+    if (dtype == PLI_BF16)
+        return head_dim == 128 ? launch_varlen_fp8<bf16_t, 128>(a, sc, tiles_upper)
+                               : launch_varlen_fp8<bf16_t, 64>(a, sc, tiles_upper);
+    return head_dim == 128 ? launch_varlen_fp8<f16_t, 128>(a, sc, tiles_upper)
+                           : launch_varlen_fp8<f16_t, 64>(a, sc, tiles_upper);
+}
+
+extern "C" int pli_kv_append_varlen_paged_fp8(const void* k_new, const void* v_new, void* k_pool, void* v_pool,
+                                              const int32_t* cu_seqlens_q, const int32_t* block_table,
+                                              const int32_t* seq_lens, const float* k_scale, const float* v_scale,
+                                              int batch, int max_tokens, int kv_heads, int head_dim, int block_size,
+                                              int num_blocks, int max_blocks_per_seq, const int64_t* strides,
+                                              int dtype, void* stream) {
+    using namespace pli;
+    clear_error();
+    PLI_REQUIRE(batch >= 0 && max_tokens >= 0 && kv_heads > 0 && head_dim > 0 && num_blocks >= 0 &&
+                    max_blocks_per_seq >= 0,
+                "pli_kv_append_varlen_paged_fp8: bad shape B=%d tokens=%d Hkv=%d D=%d blocks=%d "
+                "max_blocks_per_seq=%d",
+                batch, max_tokens, kv_heads, head_dim, num_blocks, max_blocks_per_seq);
+    PLI_REQUIRE(dtype == PLI_F32 || dtype == PLI_F16 || dtype == PLI_BF16,
+                "pli_kv_append_varlen_paged_fp8: bad dtype %d", dtype);
+    PLI_REQUIRE(block_size > 0, "pli_kv_append_varlen_paged_fp8: block_size %d must be positive", block_size);
+    PLI_REQUIRE((int64_t)max_blocks_per_seq * block_size < (1ll << 31),
+                "pli_kv_append_varlen_paged_fp8: a table row of %d blocks x %d tokens passes 2^31 keys",
+                max_blocks_per_seq, block_size);
+    // nothing to append: the (possibly NULL, pli.h) operands are not read
+    if (batch == 0 || max_tokens == 0) return PLI_OK;
+    PLI_REQUIRE(k_new && v_new && k_pool && v_pool && cu_seqlens_q && block_table && seq_lens && strides,
+                "pli_kv_append_varlen_paged_fp8: null pointer");
+    PLI_REQUIRE(num_blocks > 0 && max_blocks_per_seq > 0,
+                "pli_kv_append_varlen_paged_fp8: empty pool or table (blocks=%d max_blocks_per_seq=%d)", num_blocks,
+                max_blocks_per_seq);
+    PLI_REQUIRE(head_dim % 8 == 0 && aligned16(k_new) && aligned16(v_new) && aligned16(k_pool) && aligned16(v_pool),
+                "pli_kv_append_varlen_paged_fp8: rows of whole 8-element chunks (head_dim %% 8) and 16-byte "
+                "aligned operands required");
+    for (int i = 0; i < 10; ++i)
+        PLI_REQUIRE(strides[i] % 8 == 0, "pli_kv_append_varlen_paged_fp8: stride %d not a multiple of 8", i);
+    const int es = dtype == PLI_F32 ? 4 : 2;
+    const int cpr = head_dim / 8;
+    const int64_t total = (int64_t)max_tokens * kv_heads * cpr;
+    PLI_REQUIRE(cdiv64(total, 256) < (1ll << 31), "pli_kv_append_varlen_paged_fp8: grid too large");
+    // strides[10] as for pli_kv_append_varlen_paged: the source's in its elements, the pools' in bytes
+    const VarAppendStrides st{strides[0] * es, strides[1] * es, strides[8] * es, strides[9] * es,
+                              PagedPool{strides[2], strides[3], strides[4]},
+                              PagedPool{strides[5], strides[6], strides[7]}};
+    const PagedTable tb = paged_table(block_size, num_blocks, max_blocks_per_seq);
+    const Fp8Scales sc{k_scale, v_scale};
+    const char *kn = (const char*)k_new, *vn = (const char*)v_new;
+    char *kp = (char*)k_pool, *vp = (char*)v_pool;
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == PLI_F32)
+        return launch_varlen_append_fp8<float>(kn, vn, kp, vp, cu_seqlens_q, block_table, seq_lens, sc, batch,
+                                               max_tokens, kv_heads, cpr, st, tb, s);
+    if (dtype == PLI_BF16)
+        return launch_varlen_append_fp8<bf16_t>(kn, vn, kp, vp, cu_seqlens_q, block_table, seq_lens, sc, batch,
+                                                max_tokens, kv_heads, cpr, st, tb, s);
+    return launch_varlen_append_fp8<f16_t>(kn, vn, kp, vp, cu_seqlens_q, block_table, seq_lens, sc, batch,
+                                           max_tokens, kv_heads, cpr, st, tb, s);
 }

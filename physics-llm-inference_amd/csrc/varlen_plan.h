@@ -183,5 +183,17 @@ inline bool varlen_fast_path(int dtype, int head_dim, int heads, int kv_heads, i
         if (strides10[i] % 8 != 0) return false;
     return aligned16_operands;
 }
+// The same rule for a 1-byte (fp8 e4m3) pool, attn_varlen_paged_fp8: dtype is
+// q / o's, whose strides stay multiples of 8 elements; the pool strides
+// (strides10[2..7], in elements = bytes) are multiples of 16.
+inline bool varlen_fast_path_fp8(int dtype, int head_dim, int heads, int kv_heads, int block_size, float scale,
+                                 const int64_t* strides10, bool aligned16_operands) {
+    int64_t qo[10];
+    for (int i = 0; i < 10; ++i) qo[i] = (i >= 2 && i < 8) ? 0 : strides10[i];
+    if (!varlen_fast_path(dtype, head_dim, heads, kv_heads, block_size, scale, qo, aligned16_operands)) return false;
+    for (int i = 2; i < 8; ++i)
+        if (strides10[i] % 16 != 0) return false;
+    return true;
+}
 
 }  // namespace pli

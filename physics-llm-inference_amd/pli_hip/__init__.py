@@ -88,6 +88,17 @@ _SIGS = {
                               _vp],
     "pli_kv_append_varlen_paged": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int,
                                    _c_int, _c_int, ctypes.POINTER(_c_i64), _c_int, _vp],
+    # 1-byte (fp8 e4m3) pools: the 16-bit signatures plus k_scale, v_scale after seq_lens
+    "pli_attn_decode_paged_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int,
+                                  _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_i64), _c_f32, _c_int,
+                                  _c_int, _vp, ctypes.c_size_t, _c_int, _vp],
+    "pli_kv_append_paged_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int,
+                                _c_int, _c_int, ctypes.POINTER(_c_i64), _c_int, _vp],
+    "pli_attn_varlen_paged_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int,
+                                  _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_i64), _c_f32, _c_int,
+                                  _c_int, _vp],
+    "pli_kv_append_varlen_paged_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int,
+                                       _c_int, _c_int, _c_int, ctypes.POINTER(_c_i64), _c_int, _vp],
     # tuning entry points (include/pli.h tuning section): explicit kernel variant
     "pli_flash_attn_fwd_variant": [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int,
                                    _c_int, ctypes.POINTER(_c_i64), _c_f32, _c_int, _c_int, _vp,
@@ -542,6 +553,182 @@ def kv_append_varlen_paged(k_new: torch.Tensor, v_new: torch.Tensor, k_pool: tor
                                               block_table.shape[0], T, Hkv, D, bs, num_blocks, block_table.shape[1],
                                               st, _dtype_code(k_new), _stream(dev))
     _check(rc, "pli_kv_append_varlen_paged")
+
+
+# ------------------------------------------- 1-byte (fp8 e4m3) paged KV cache
+FP8_POOL_DTYPES = (torch.float8_e4m3fn, torch.uint8)
+
+
+def _check_fp8(what: str, x: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, k_scale, v_scale,
+               ints: dict):
+    """shared checks of the fp8 calls: x (q or k_new) fp32 / fp16 / bf16 with D last, the pools
+    [num_blocks, block_size, Hkv, D] views of torch.float8_e4m3fn or torch.uint8 (any page stride), the scales
+    fp32 [Hkv] on the device or None (all ones), the named int32 tensors contiguous; returns the device"""
+    dev = _require_gpu(x)
+    _dtype_code(x)
+    for name, t in (("k_pool", k_pool), ("v_pool", v_pool)):
+        if not t.is_cuda or t.device != dev or t.dtype not in FP8_POOL_DTYPES or t.dtype != k_pool.dtype:
+            raise PliError(f"{what}: {name} must be a torch.float8_e4m3fn or torch.uint8 tensor on {dev}, "
+                           f"got {t.dtype} on {t.device}")
+    for name, t in ints.items():
+        if not t.is_cuda or t.device != dev or t.dtype != torch.int32 or not t.is_contiguous():
+            raise PliError(f"{what}: {name} must be a contiguous int32 tensor on {dev}")
+    if k_pool.dim() != 4 or tuple(v_pool.shape) != tuple(k_pool.shape) or k_pool.shape[3] != x.shape[-1]:
+        raise PliError(f"{what} expects [num_blocks, block_size, Hkv, D] pools with the tokens' D, got "
+                       f"{tuple(x.shape)} k{tuple(k_pool.shape)} v{tuple(v_pool.shape)}")
+    for name, t in (("k_scale", k_scale), ("v_scale", v_scale)):
+        if t is not None and (not t.is_cuda or t.device != dev or t.dtype != torch.float32 or
+                              tuple(t.shape) != (k_pool.shape[2],) or not t.is_contiguous()):
+            raise PliError(f"{what}: {name} must be None or a contiguous fp32 [{k_pool.shape[2]}] tensor on {dev}")
+    if any(t.stride(-1) != 1 for t in (x, k_pool, v_pool) if t.numel()):
+        raise PliError(f"{what}: a unit head_dim stride is required (the pools are used in place)")
+    return dev
+
+
+def attn_decode_paged_fp8(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor,
+                          block_table: torch.Tensor, seq_lens: torch.Tensor, k_scale: torch.Tensor | None = None,
+                          v_scale: torch.Tensor | None = None, *, scale: float | None = None,
+                          causal: bool = True, n_kv_add: int = 0, max_kv: int | None = None,
+                          out: torch.Tensor | None = None, workspace: torch.Tensor | None = None
+                          ) -> torch.Tensor:
+    """attn_decode_paged over 1-byte pools of fp8 e4m3fn codes (torch.float8_e4m3fn or torch.uint8 views), an
+    element's value being code * scale[kv head]: k_scale / v_scale fp32 [Hkv] device tensors read on the device
+    (graph-replayable), None for all ones.  q and the output are bf16 / fp16 (MFMA kernel) or fp32."""
+    dev = _check_fp8("attn_decode_paged_fp8", q, k_pool, v_pool, k_scale, v_scale,
+                     {"block_table": block_table, "seq_lens": seq_lens})
+    if q.dim() != 4 or block_table.dim() != 2 or block_table.shape[0] != q.shape[0] or \
+            tuple(seq_lens.shape) != (q.shape[0],):
+        raise PliError(f"attn_decode_paged_fp8: shape mismatch q{tuple(q.shape)} table{tuple(block_table.shape)} "
+                       f"seq_lens{tuple(seq_lens.shape)}")
+    B, Sq, H, D = q.shape
+    num_blocks, bs, Hkv, _ = k_pool.shape
+    max_blocks = block_table.shape[1]
+    if Hkv == 0 or H % Hkv != 0:
+        raise PliError(f"heads {H} not a multiple of kv heads {Hkv}")
+    cap = max_blocks * bs
+    max_kv = cap if max_kv is None else int(max_kv)
+    if not 0 <= max_kv <= cap:
+        raise PliError(f"max_kv {max_kv} outside the table row [0, {cap}]")
+    if out is None:
+        out = torch.empty((B, Sq, H, D), device=q.device, dtype=q.dtype)
+    _require_gpu(q, out)
+    if tuple(out.shape) != (B, Sq, H, D) or (out.numel() and out.stride(-1) != 1):
+        raise PliError("bad output tensor")
+    if scale is None:
+        scale = D ** -0.5
+    st = (_c_i64 * 12)(*(int(x) for x in (q.stride(0), q.stride(2), q.stride(1),
+                                          k_pool.stride(0), k_pool.stride(1), k_pool.stride(2),
+                                          v_pool.stride(0), v_pool.stride(1), v_pool.stride(2),
+                                          out.stride(0), out.stride(2), out.stride(1))))
+    ws_bytes = int(lib().pli_attn_decode_paged_workspace_size(B, H, Hkv, Sq, max_kv, D))
+    if workspace is None or workspace.numel() * workspace.element_size() < ws_bytes:
+        workspace = torch.empty(max(ws_bytes // 4, 1), device=q.device, dtype=torch.float32)
+    with _on_device(dev):
+        rc = lib().pli_attn_decode_paged_fp8(_ptr(q), _ptr(k_pool), _ptr(v_pool), _ptr(out), _ptr(block_table),
+                                             _ptr(seq_lens), _ptr(k_scale), _ptr(v_scale), B, H, Hkv, Sq, D, bs,
+                                             num_blocks, max_blocks, max_kv, st, float(scale), int(bool(causal)),
+                                             int(n_kv_add), _ptr(workspace), ws_bytes, _dtype_code(q), _stream(dev))
+    _check(rc, "pli_attn_decode_paged_fp8")
+    return out
+
+
+def kv_append_paged_fp8(k_new: torch.Tensor, v_new: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor,
+                        block_table: torch.Tensor, seq_lens: torch.Tensor, k_scale: torch.Tensor | None = None,
+                        v_scale: torch.Tensor | None = None) -> None:
+    """kv_append_paged into 1-byte pools: k_new / v_new [B, T, Hkv, D] (fp32 / fp16 / bf16) are stored as
+    e4m3fn(clamp(x / scale[kv head], -448, 448)), round to nearest even, NaN kept."""
+    dev = _check_fp8("kv_append_paged_fp8", k_new, k_pool, v_pool, k_scale, v_scale,
+                     {"block_table": block_table, "seq_lens": seq_lens})
+    _require_gpu(k_new, v_new)
+    if k_new.dim() != 4 or tuple(v_new.shape) != tuple(k_new.shape) or k_pool.shape[2] != k_new.shape[2] or \
+            (v_new.numel() and v_new.stride(-1) != 1) or block_table.dim() != 2 or \
+            block_table.shape[0] != k_new.shape[0] or tuple(seq_lens.shape) != (k_new.shape[0],):
+        raise PliError(f"kv_append_paged_fp8 shape mismatch new{tuple(k_new.shape)} v{tuple(v_new.shape)} "
+                       f"pool{tuple(k_pool.shape)} table{tuple(block_table.shape)} seq_lens{tuple(seq_lens.shape)}")
+    B, T, Hkv, D = k_new.shape
+    num_blocks, bs = k_pool.shape[0], k_pool.shape[1]
+    st = (_c_i64 * 12)(*(int(x) for x in (k_new.stride(0), k_new.stride(2), k_new.stride(1),
+                                          k_pool.stride(0), k_pool.stride(1), k_pool.stride(2),
+                                          v_pool.stride(0), v_pool.stride(1), v_pool.stride(2),
+                                          v_new.stride(0), v_new.stride(2), v_new.stride(1))))
+    with _on_device(dev):
+        rc = lib().pli_kv_append_paged_fp8(_ptr(k_new), _ptr(v_new), _ptr(k_pool), _ptr(v_pool), _ptr(block_table),
+                                           _ptr(seq_lens), _ptr(k_scale), _ptr(v_scale), B, T, Hkv, D, bs,
+                                           num_blocks, block_table.shape[1], st, _dtype_code(k_new), _stream(dev))
+    _check(rc, "pli_kv_append_paged_fp8")
+
+
+def _check_varlen_fp8(what: str, x: torch.Tensor, k_pool, v_pool, k_scale, v_scale, block_table, seq_lens,
+                      cu_seqlens_q):
+    dev = _check_fp8(what, x, k_pool, v_pool, k_scale, v_scale,
+                     {"block_table": block_table, "seq_lens": seq_lens, "cu_seqlens_q": cu_seqlens_q})
+    B = seq_lens.shape[0] if seq_lens.dim() == 1 else -1
+    if x.dim() != 3 or block_table.dim() != 2 or block_table.shape[0] != B or tuple(cu_seqlens_q.shape) != (B + 1,):
+        raise PliError(f"{what}: shape mismatch tokens{tuple(x.shape)} table{tuple(block_table.shape)} "
+                       f"seq_lens{tuple(seq_lens.shape)} cu_seqlens_q{tuple(cu_seqlens_q.shape)}")
+    return dev
+
+
+def attn_varlen_paged_fp8(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor,
+                          seq_lens: torch.Tensor, cu_seqlens_q: torch.Tensor, k_scale: torch.Tensor | None = None,
+                          v_scale: torch.Tensor | None = None, max_kv: int | None = None,
+                          scale: float | None = None, causal: bool = True,
+                          out: torch.Tensor | None = None) -> torch.Tensor:
+    """attn_varlen_paged over 1-byte pools of fp8 e4m3fn codes; pools and scales as for attn_decode_paged_fp8."""
+    dev = _check_varlen_fp8("attn_varlen_paged_fp8", q, k_pool, v_pool, k_scale, v_scale, block_table, seq_lens,
+                            cu_seqlens_q)
+    T, H, D = q.shape
+    num_blocks, bs, Hkv, _ = k_pool.shape
+    B, max_blocks = block_table.shape
+    if Hkv == 0 or H % Hkv != 0:
+        raise PliError(f"heads {H} not a multiple of kv heads {Hkv}")
+    cap = max_blocks * bs
+    max_kv = cap if max_kv is None else int(max_kv)
+    if not 0 <= max_kv <= cap:
+        raise PliError(f"max_kv {max_kv} outside the table row [0, {cap}]")
+    if out is None:
+        out = torch.empty((T, H, D), device=q.device, dtype=q.dtype)
+    _require_gpu(q, out)
+    if tuple(out.shape) != (T, H, D) or (out.numel() and out.stride(-1) != 1):
+        raise PliError("bad output tensor")
+    if scale is None:
+        scale = D ** -0.5
+    st = (_c_i64 * 10)(*(int(x) for x in (q.stride(0), q.stride(1),
+                                          k_pool.stride(0), k_pool.stride(1), k_pool.stride(2),
+                                          v_pool.stride(0), v_pool.stride(1), v_pool.stride(2),
+                                          out.stride(0), out.stride(1))))
+    with _on_device(dev):
+        rc = lib().pli_attn_varlen_paged_fp8(_ptr(q), _ptr(k_pool), _ptr(v_pool), _ptr(out), _ptr(cu_seqlens_q),
+                                             _ptr(block_table), _ptr(seq_lens), _ptr(k_scale), _ptr(v_scale), B, T,
+                                             H, Hkv, D, bs, num_blocks, max_blocks, max_kv, st, float(scale),
+                                             int(bool(causal)), _dtype_code(q), _stream(dev))
+    _check(rc, "pli_attn_varlen_paged_fp8")
+    return out
+
+
+def kv_append_varlen_paged_fp8(k_new: torch.Tensor, v_new: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor,
+                               block_table: torch.Tensor, seq_lens: torch.Tensor, cu_seqlens_q: torch.Tensor,
+                               k_scale: torch.Tensor | None = None, v_scale: torch.Tensor | None = None) -> None:
+    """kv_append_varlen_paged into 1-byte pools; quantisation as for kv_append_paged_fp8."""
+    dev = _check_varlen_fp8("kv_append_varlen_paged_fp8", k_new, k_pool, v_pool, k_scale, v_scale, block_table,
+                            seq_lens, cu_seqlens_q)
+    _require_gpu(k_new, v_new)
+    T, Hkv, D = k_new.shape
+    if tuple(v_new.shape) != tuple(k_new.shape) or k_pool.shape[2] != Hkv or (v_new.numel() and v_new.stride(-1) != 1):
+        raise PliError(f"kv_append_varlen_paged_fp8 shape mismatch new{tuple(k_new.shape)} v{tuple(v_new.shape)} "
+                       f"pool{tuple(k_pool.shape)}")
+    num_blocks, bs = k_pool.shape[0], k_pool.shape[1]
+    st = (_c_i64 * 10)(*(int(x) for x in (k_new.stride(0), k_new.stride(1),
+                                          k_pool.stride(0), k_pool.stride(1), k_pool.stride(2),
+                                          v_pool.stride(0), v_pool.stride(1), v_pool.stride(2),
+                                          v_new.stride(0), v_new.stride(1))))
+    with _on_device(dev):
+        rc = lib().pli_kv_append_varlen_paged_fp8(_ptr(k_new), _ptr(v_new), _ptr(k_pool), _ptr(v_pool),
+                                                  _ptr(cu_seqlens_q), _ptr(block_table), _ptr(seq_lens),
+                                                  _ptr(k_scale), _ptr(v_scale), block_table.shape[0], T, Hkv, D, bs,
+                                                  num_blocks, block_table.shape[1], st, _dtype_code(k_new),
+                                                  _stream(dev))
+    _check(rc, "pli_kv_append_varlen_paged_fp8")
 
 
 # ---------------------------------------------------------------------- MoE
