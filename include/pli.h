@@ -550,6 +550,81 @@ int pli_kv_append_varlen_paged_fp8(const void* k_new, const void* v_new,
                                    const int64_t* strides, int dtype,
                                    void* stream);
 
+/* Split-K for the packed calls: pli_attn_varlen_paged / _fp8 with a caller
+ * workspace.  The plain calls give a 64-row tile one workgroup that walks all
+ * of the tile's keys; these cut the tile's key range [0, key_end) into chunks
+ * of `span` keys, give every chunk a workgroup, and merge the chunks' fp32
+ * partials in a second kernel.  The plain calls are untouched.
+ *
+ * split_keys: > 0 the span, a multiple of 64; 0 the plan's choice, span =
+ *   max(2048, round-up-to-64(ceil(max_kv / 16))): at most 16 chunks per tile
+ *   whatever max_kv is, and no split at all up to 2048 keys.  splits_max = max(1, ceil(max_kv / span)) is the
+ *   number of chunks the grid provides per tile.  span and splits_max depend
+ *   on the host arguments only (pli_attn_varlen_paged_split_plan reports
+ *   them), so the grid and the workspace replay in a captured graph while
+ *   cu_seqlens_q, block_table and seq_lens change in place; a tile uses
+ *   max(1, ceil(key_end / span)) of its chunks, counted on the device, and
+ *   the other workgroups leave before any K / V load.
+ * workspace: pli_attn_varlen_paged_workspace_size bytes = splits_max *
+ *   max_tokens * heads * (head_dim + 2) * 4 (fp32 partial O, then (m, l) per
+ *   (chunk, packed token, head)), 16-byte aligned; it need not be initialised
+ *   and holds nothing between calls.  The size is 0 when splits_max == 1 or
+ *   when the shape (head_dim, heads / kv_heads) can only take the generic
+ *   kernel; the workspace may then be NULL.
+ * Routes (pli_last_route): "attn_varlen_paged_split+attn_varlen_paged_combine"
+ *   or "attn_varlen_paged_split_fp8+attn_varlen_paged_combine"; when
+ *   splits_max == 1 the call IS the plain call ("attn_varlen_paged" /
+ *   "attn_varlen_paged_fp8", same kernel, same cost); when the MFMA kernel's
+ *   rule fails the generic kernel runs as in the plain call and the workspace
+ *   is not used.  Rows of a tile with one chunk are bitwise those of the plain
+ *   call; rows merged from several chunks differ from it by fp32 rounding.
+ * Which call: the _ws call wins where tiles are few and long -- decode rows
+ *   or one prompt chunk at long context, alone or inside a mixed step
+ *   (measured 1.7x - 4.3x over the plain call at 32k keys, 2.6x - 6.3x over
+ *   an fp8 pool).  A step whose tiles already fill the device (about a
+ *   thousand workgroups of 4k keys each) is 1.17x SLOWER when it is cut in
+ *   two and 1.9x slower when max_kv is 32k while every sequence holds 4k:
+ *   such a step should take the plain call, and every caller should pass the
+ *   max_kv it needs rather than the pool's.  Decode-only batches stay on
+ *   pli_attn_decode_paged (1.25x faster than this call).  DESIGN.md section
+ *   3.2e has the numbers.
+ * PLI_EINVAL before any HIP call: everything the plain calls reject, a
+ *   negative split_keys or one that is not a multiple of 64, a NULL,
+ *   misaligned or short workspace when the size is > 0, a grid past 2^31.
+ *   Empty calls (batch == 0 or max_tokens == 0) return PLI_OK and their
+ *   operands may be NULL.  Nothing is allocated or synchronised. */
+size_t pli_attn_varlen_paged_workspace_size(int batch, int max_tokens, int heads,
+                                            int kv_heads, int max_kv,
+                                            int head_dim, int split_keys);
+int pli_attn_varlen_paged_split_plan(int batch, int max_tokens, int heads,
+                                     int kv_heads, int max_kv, int head_dim,
+                                     int split_keys, int* span,
+                                     int* splits_max);
+int pli_attn_varlen_paged_ws(const void* q, const void* k_pool,
+                             const void* v_pool, void* o,
+                             const int32_t* cu_seqlens_q,
+                             const int32_t* block_table,
+                             const int32_t* seq_lens, int batch, int max_tokens,
+                             int heads, int kv_heads, int head_dim,
+                             int block_size, int num_blocks,
+                             int max_blocks_per_seq, int max_kv,
+                             const int64_t* strides, float scale, int causal,
+                             int dtype, int split_keys, void* workspace,
+                             size_t workspace_bytes, void* stream);
+int pli_attn_varlen_paged_fp8_ws(const void* q, const void* k_pool,
+                                 const void* v_pool, void* o,
+                                 const int32_t* cu_seqlens_q,
+                                 const int32_t* block_table,
+                                 const int32_t* seq_lens, const float* k_scale,
+                                 const float* v_scale, int batch,
+                                 int max_tokens, int heads, int kv_heads,
+                                 int head_dim, int block_size, int num_blocks,
+                                 int max_blocks_per_seq, int max_kv,
+                                 const int64_t* strides, float scale,
+                                 int causal, int dtype, int split_keys,
+                                 void* workspace, size_t workspace_bytes,
+                                 void* stream);
+
 /* ------------------------------------------------------------------------
  * Tuning section: the same operations with an explicit kernel choice, for
  * A/B runs (tools/tune.py) and the per-variant parity tests.  Not part of

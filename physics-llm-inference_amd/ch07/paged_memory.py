@@ -34,6 +34,7 @@ same memory holds twice the tokens.
 """
 from __future__ import annotations
 
+import functools
 from dataclasses import dataclass, field
 
 import torch
@@ -65,6 +66,19 @@ class _CacheOptions(type):
         self.kv_dtype = kv_dtype
         self.__init__(*args, **kwargs)
         return self
+
+
+def _workspace_keyword(method):
+    """``attend_packed`` keeps its parameter list too (the same test pins it),
+    so its trailing keyword ``workspace=`` is taken here, as ``kv_dtype`` is
+    above: None (the default) is the method as written, a tensor goes to
+    ``_attend_packed_ws`` with the method's own arguments."""
+    @functools.wraps(method)
+    def call(self, *args, workspace: torch.Tensor | None = None, **kwargs):
+        if workspace is None:
+            return method(self, *args, **kwargs)
+        return self._attend_packed_ws(*args, workspace=workspace, **kwargs)
+    return call
 
 
 class PagedKVCache(metaclass=_CacheOptions):
@@ -250,12 +264,46 @@ class PagedKVCache(metaclass=_CacheOptions):
             return
         pli_hip.kv_append_varlen_paged(k_new, v_new, k_pool, v_pool, block_table, seq_lens, cu_seqlens_q)
 
+    def packed_workspace_bytes(self, batch: int, max_tokens: int, q_heads: int, max_blocks: int | None = None) -> int:
+        """Bytes ``attend_packed(..., workspace=)`` needs for a step of
+        ``batch`` requests and ``max_tokens`` packed rows of ``q_heads`` heads
+        over tables ``max_blocks`` wide (default: the whole pool): the size
+        pli_attn_varlen_paged_workspace_size reports, 0 when the keys are too
+        few to split."""
+        width = self.num_blocks if max_blocks is None else int(max_blocks)
+        return pli_hip.attn_varlen_paged_workspace_bytes(batch, max_tokens, q_heads, self.num_heads,
+                                                         width * self.block_size, self.head_dim)
+
+    def packed_workspace(self, batch: int, max_tokens: int, q_heads: int, max_blocks: int | None = None):
+        """A float32 device tensor of ``packed_workspace_bytes(...)`` bytes (at
+        least one element) for ``attend_packed``; it need not be initialised
+        and can be reused by every layer and step of the same sizes."""
+        if self.k_cache is None:
+            raise pli_hip.PliError("PagedKVCache has no device pools (created off-device)")
+        need = self.packed_workspace_bytes(batch, max_tokens, q_heads, max_blocks)
+        return torch.empty(max(need // 4, 1), dtype=torch.float32, device=self.k_cache.device)
+
+    def _attend_packed_ws(self, layer: int, q: torch.Tensor, block_table: torch.Tensor, seq_lens: torch.Tensor,
+                          cu_seqlens_q: torch.Tensor, causal: bool = True, *, workspace: torch.Tensor) -> torch.Tensor:
+        """attend_packed through the split-K calls (pli_attn_varlen_paged_ws /
+        _fp8_ws) with the plan's own span"""
+        k_pool, v_pool = self._pools(layer)
+        if self.kv_dtype is not None:
+            return pli_hip.attn_varlen_paged_fp8(q, k_pool, v_pool, block_table, seq_lens, cu_seqlens_q,
+                                                 self.k_scale[layer], self.v_scale[layer], causal=causal,
+                                                 workspace=workspace)
+        return pli_hip.attn_varlen_paged(q, k_pool, v_pool, block_table, seq_lens, cu_seqlens_q, causal=causal,
+                                         workspace=workspace)
+
+    @_workspace_keyword
     def attend_packed(self, layer: int, q: torch.Tensor, block_table: torch.Tensor, seq_lens: torch.Tensor,
                       cu_seqlens_q: torch.Tensor, causal: bool = True) -> torch.Tensor:
         """Attention of packed q [tokens, Hq, head_dim] over each sequence's
         own pages and length in one launch, prompt chunks and decode rows
         mixed; causal masks bottom-right per sequence.  Returns [tokens, Hq,
-        head_dim]."""
+        head_dim].  The keyword ``workspace=`` (a ``packed_workspace(...)``
+        tensor; default None, this call as it is) makes the split-K call, which
+        gives a long sequence's tile several workgroups."""
         k_pool, v_pool = self._pools(layer)
         if self.kv_dtype is not None:
             return pli_hip.attn_varlen_paged_fp8(q, k_pool, v_pool, block_table, seq_lens, cu_seqlens_q,
@@ -294,6 +342,10 @@ Mixed steps (prompt chunks and decode rows in one launch):
     a tile; the four waves of a workgroup share each 32-key K/V image, loaded
     once through the block table, and a tile stops at its last row's causal
     limit.  tables_packed / append_packed / attend_packed drive it.
+  - With a workspace (packed_workspace, attend_packed(..., workspace=ws)) a
+    tile's keys are cut into chunks that run as workgroups of their own and
+    are merged by a second kernel (pli_attn_varlen_paged_ws): a decode row at
+    long context no longer walks all its keys in one workgroup.
 
 A 1-byte cache (kv_dtype=torch.float8_e4m3fn):
   - The pools hold OCP fp8 e4m3 codes, value = code * scale[layer, kv head];

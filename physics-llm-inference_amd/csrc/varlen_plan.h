@@ -3,7 +3,9 @@
 // position rule, the address clamps and the fast/generic rule that the
 // kernels of varlen_attn.hip use.  Every function carries PLI_HD
 // (paged_plan.h), so the same text runs in the kernels and in
-// tests/host/varlen_plan_check.cpp (tests/test_varlen_plan.py).
+// tests/host/varlen_plan_check.cpp (tests/test_varlen_plan.py).  The split-K
+// section (chunks of a tile's key range, the workspace rows) is replayed by
+// tests/host/varlen_split_check.cpp (tests/test_varlen_split_plan.py).
 //
 // Operands: q / o packed [max_tokens, heads, head_dim]; cu_seqlens_q int32
 // [batch + 1], sequence b owns packed tokens cu[b] .. cu[b+1] - 1; seq_lens[b]
@@ -124,6 +126,89 @@ PLI_HD inline int varlen_key_end(int n_kv, int q_len, int tile, int tpt, int cau
     const int i_last = (int)(end < q_len ? end : q_len) - 1;
     if (i_last < 0) return 0;
     return varlen_row_limit(n_kv, q_len, i_last, causal) + 1;
+}
+
+// ---- split-K ------------------------------------------------------------------
+// A tile's key range [0, key_end) is cut into chunks of `span` keys (a multiple
+// of 64, so a chunk starts on an even 32-key step): chunk s covers
+// [s * span, min((s + 1) * span, key_end)), and a tile has
+// chunks = max(1, ceil(key_end / span)) of them -- a tile that sees no key keeps
+// one (empty) chunk, whose workgroup writes its rows as 0.  The grid holds
+// splits_max = max(1, ceil(max_kv / span)) workgroups per tile and kv head;
+// those with s >= chunks leave before any K / V load.  span and splits_max
+// depend on host arguments only.
+constexpr int VAR_SPAN_UNIT = 2 * VAR_STEP;      // 64: spans are multiples of it
+// split_keys == 0: no chunk shorter than VAR_SPAN_MIN keys and no more than VAR_SPLITS_CAP chunks per tile.
+// Measured: spans of 2048 - 4096 keys are the best on the long-context shapes, and a
+// step whose tiles already fill the device loses to the plain call whenever it is cut at all.
+constexpr int VAR_SPAN_MIN = 2048;
+constexpr int VAR_SPLITS_CAP = 16;
+struct VarSplitPlan {
+    int span;                 // keys per chunk
+    int splits_max;           // chunks the grid provides per tile; 1: no split, no workspace
+    int64_t workspace_bytes;  // splits_max * max_tokens * heads * (head_dim + 2) * 4, or 0
+};
+// split_keys > 0: the caller's span (the caller checks % 64); 0: the plan's.
+// A shape only the generic kernel takes (head_dim, group size) is never split.
+inline VarSplitPlan varlen_split_plan(int max_tokens, int heads, int kv_heads, int max_kv, int head_dim,
+                                      int split_keys) {
+    int64_t span = split_keys;
+    if (span <= 0) {
+        const int64_t per = ((int64_t)max_kv + VAR_SPLITS_CAP - 1) / VAR_SPLITS_CAP;
+        span = (per + VAR_SPAN_UNIT - 1) / VAR_SPAN_UNIT * VAR_SPAN_UNIT;
+        if (span < VAR_SPAN_MIN) span = VAR_SPAN_MIN;
+    }
+    int64_t splits = ((int64_t)max_kv + span - 1) / span;
+    const int G = kv_heads > 0 && heads % kv_heads == 0 ? heads / kv_heads : 0;
+    const bool mfma_shape = (head_dim == 64 || head_dim == 128) && (G == 1 || G == 2 || G == 4 || G == 8 || G == 16);
+    if (splits < 1 || !mfma_shape || max_tokens <= 0) splits = 1;
+    VarSplitPlan p;
+    p.span = (int)(span > 0x7fffffc0 ? 0x7fffffc0 : span);
+    p.splits_max = (int)splits;
+    p.workspace_bytes = 0;
+    if (splits > 1) {
+        // splits <= 2^25, max_tokens and heads < 2^31 each: take the factors one at a time and saturate (no
+        // such workspace exists, and the call rejects the grid before it looks at the workspace)
+        const int64_t row = ((int64_t)head_dim + 2) * 4, top = INT64_MAX / row;
+        int64_t rows = splits * max_tokens;  // < 2^56
+        rows = rows > top / heads ? top : rows * heads;
+        p.workspace_bytes = rows >= top ? INT64_MAX / 16 * 16 : rows * row;
+    }
+    return p;
+}
+PLI_HD inline int varlen_chunks(int key_end, int span) {
+    const int64_t n = ((int64_t)key_end + span - 1) / span;
+    return n < 1 ? 1 : (int)n;
+}
+// chunks of tile `tile` of a sequence, from the device tensors' entries: the
+// one function the split kernel (per tile) and the combine kernel (per row,
+// tile = i / tpt) both call.  key_end <= n_kv <= max_kv, so the count never
+// passes splits_max; the clamp only states it.
+PLI_HD inline int varlen_tile_chunks(int cu_b, int cu_b1, int seq_len, int max_kv, int tile, int tpt, int causal,
+                                     int span, int splits_max) {
+    const int n = varlen_chunks(
+        varlen_key_end(varlen_n_kv(seq_len, max_kv), varlen_q_len(cu_b, cu_b1), tile, tpt, causal), span);
+    return n > splits_max ? splits_max : n;
+}
+// tile of token i (0 <= i < q_len) of a sequence; tpt >= 4, so it fits an int
+PLI_HD inline int varlen_row_tile(int64_t i, int tpt) {
+    const int64_t t = i < 0 ? 0 : i / tpt;
+    return t > 0x7fffffff ? 0x7fffffff : (int)t;
+}
+// chunk s of a tile: keys [begin, end), begin a multiple of 64
+PLI_HD inline int varlen_chunk_begin(int s, int span) {
+    const int64_t k = (int64_t)s * span;
+    return k > 0x7fffffc0 ? 0x7fffffc0 : (int)k;
+}
+PLI_HD inline int varlen_chunk_end(int s, int span, int key_end) {
+    const int64_t k = ((int64_t)s + 1) * span;
+    return k < key_end ? (int)k : key_end;
+}
+// fp32 partial row of (chunk s, packed token, head) in the workspace, in rows:
+// partial O holds head_dim floats per row, the (m, l) pairs follow all of O.
+// The token is a clamped one (varlen_token), s < splits_max.
+PLI_HD inline int64_t varlen_partial_row(int s, int tok, int h, int max_tokens, int heads) {
+    return ((int64_t)s * max_tokens + tok) * heads + h;
 }
 
 // ---- append -------------------------------------------------------------------

@@ -99,6 +99,15 @@ _SIGS = {
                                   _c_int, _vp],
     "pli_kv_append_varlen_paged_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int,
                                        _c_int, _c_int, _c_int, ctypes.POINTER(_c_i64), _c_int, _vp],
+    # split-K packed calls: the plain signatures plus split_keys, workspace, workspace_bytes before the stream
+    "pli_attn_varlen_paged_workspace_size": [_c_int] * 7,
+    "pli_attn_varlen_paged_split_plan": [_c_int] * 7 + [ctypes.POINTER(_c_int), ctypes.POINTER(_c_int)],
+    "pli_attn_varlen_paged_ws": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int,
+                                 _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_i64), _c_f32, _c_int, _c_int,
+                                 _c_int, _vp, ctypes.c_size_t, _vp],
+    "pli_attn_varlen_paged_fp8_ws": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int,
+                                     _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_i64), _c_f32, _c_int,
+                                     _c_int, _c_int, _vp, ctypes.c_size_t, _vp],
     # tuning entry points (include/pli.h tuning section): explicit kernel variant
     "pli_flash_attn_fwd_variant": [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int,
                                    _c_int, ctypes.POINTER(_c_i64), _c_f32, _c_int, _c_int, _vp,
@@ -486,10 +495,54 @@ def _check_varlen(what: str, x: torch.Tensor, k_pool: torch.Tensor, v_pool: torc
     return dev
 
 
+def attn_varlen_paged_workspace_bytes(batch: int, max_tokens: int, heads: int, kv_heads: int, max_kv: int,
+                                      head_dim: int, split_keys: int = 0) -> int:
+    """bytes of workspace the split-K packed calls (attn_varlen_paged / attn_varlen_paged_fp8 with workspace=)
+    need for these host arguments (pli_attn_varlen_paged_workspace_size); 0: the call is the plain call"""
+    return int(lib().pli_attn_varlen_paged_workspace_size(int(batch), int(max_tokens), int(heads), int(kv_heads),
+                                                          int(max_kv), int(head_dim), int(split_keys)))
+
+
+def attn_varlen_paged_split_plan(batch: int, max_tokens: int, heads: int, kv_heads: int, max_kv: int, head_dim: int,
+                                 split_keys: int = 0) -> tuple:
+    """(span, splits_max) of the split-K packed calls for these host arguments (pli_attn_varlen_paged_split_plan)"""
+    span, splits = _c_int(0), _c_int(0)
+    rc = lib().pli_attn_varlen_paged_split_plan(int(batch), int(max_tokens), int(heads), int(kv_heads), int(max_kv),
+                                                int(head_dim), int(split_keys), ctypes.byref(span),
+                                                ctypes.byref(splits))
+    _check(rc, "pli_attn_varlen_paged_split_plan")
+    return span.value, splits.value
+
+
+def _varlen_workspace(what: str, workspace, split_keys: int, q, k_pool, block_table, max_kv) -> int:
+    """checks of the workspace= keyword, made on shapes alone and before the operands' own: a contiguous fp32
+    tensor of at least the bytes the call needs, on a GPU; returns those bytes"""
+    if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.float32 or not workspace.is_contiguous():
+        raise PliError(f"{what}: workspace must be a contiguous torch.float32 tensor")
+    split_keys = int(split_keys)
+    if split_keys < 0 or split_keys % 64:
+        raise PliError(f"{what}: split_keys {split_keys} must be 0 or a positive multiple of 64")
+    if q.dim() != 3 or k_pool.dim() != 4 or block_table.dim() != 2:
+        raise PliError(f"{what}: shape mismatch tokens{tuple(q.shape)} pool{tuple(k_pool.shape)} "
+                       f"table{tuple(block_table.shape)}")
+    cap = block_table.shape[1] * k_pool.shape[1]
+    need = attn_varlen_paged_workspace_bytes(block_table.shape[0], q.shape[0], q.shape[1], k_pool.shape[2],
+                                             cap if max_kv is None else int(max_kv), q.shape[2], split_keys)
+    have = workspace.numel() * workspace.element_size()
+    if have < need:
+        raise PliError(f"{what}: workspace of {need} bytes needed, {have} given")
+    if not workspace.is_cuda:
+        raise PliError(f"{what}: workspace is a CPU tensor")
+    if workspace.device != q.device:
+        raise PliError(f"{what}: workspace on {workspace.device}, q on {q.device}")
+    return need
+
+
 def attn_varlen_paged(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor,
                       seq_lens: torch.Tensor, cu_seqlens_q: torch.Tensor, max_kv: int | None = None,
                       scale: float | None = None, causal: bool = True,
-                      out: torch.Tensor | None = None) -> torch.Tensor:
+                      out: torch.Tensor | None = None, workspace: torch.Tensor | None = None,
+                      split_keys: int = 0) -> torch.Tensor:
     """Attention of a packed, mixed batch straight over a paged pool: q
     [max_tokens, Hq, D], sequence b owning rows cu_seqlens_q[b] ..
     cu_seqlens_q[b+1] - 1 (any count, 0 included); k_pool / v_pool
@@ -498,7 +551,13 @@ def attn_varlen_paged(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tenso
     step's tokens already appended (clamped to max_kv, default max_blocks *
     block_size).  causal masks bottom-right per sequence.  The three int32
     tensors are read on the device (graph-replayable).  Returns [max_tokens, Hq,
-    D]; a row that sees no key is 0, rows past cu_seqlens_q[B] are not written."""
+    D]; a row that sees no key is 0, rows past cu_seqlens_q[B] are not written.
+    workspace: None makes the plain call; a float32 device tensor of at least
+    attn_varlen_paged_workspace_bytes(...) bytes makes the split-K call
+    (pli_attn_varlen_paged_ws), which cuts every tile's key range into chunks
+    of split_keys keys (a multiple of 64; 0: the plan's choice)."""
+    if workspace is not None:
+        _varlen_workspace("attn_varlen_paged", workspace, split_keys, q, k_pool, block_table, max_kv)
     dev = _check_varlen("attn_varlen_paged", q, k_pool, v_pool, block_table, seq_lens, cu_seqlens_q)
     T, H, D = q.shape
     num_blocks, bs, Hkv, _ = k_pool.shape
@@ -521,6 +580,14 @@ def attn_varlen_paged(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tenso
                                           v_pool.stride(0), v_pool.stride(1), v_pool.stride(2),
                                           out.stride(0), out.stride(1))))
     with _on_device(dev):
+        if workspace is not None:
+            rc = lib().pli_attn_varlen_paged_ws(_ptr(q), _ptr(k_pool), _ptr(v_pool), _ptr(out), _ptr(cu_seqlens_q),
+                                                _ptr(block_table), _ptr(seq_lens), B, T, H, Hkv, D, bs, num_blocks,
+                                                max_blocks, max_kv, st, float(scale), int(bool(causal)),
+                                                _dtype_code(q), int(split_keys), _ptr(workspace),
+                                                workspace.numel() * workspace.element_size(), _stream(dev))
+            _check(rc, "pli_attn_varlen_paged_ws")
+            return out
         rc = lib().pli_attn_varlen_paged(_ptr(q), _ptr(k_pool), _ptr(v_pool), _ptr(out), _ptr(cu_seqlens_q),
                                          _ptr(block_table), _ptr(seq_lens), B, T, H, Hkv, D, bs, num_blocks,
                                          max_blocks, max_kv, st, float(scale), int(bool(causal)), _dtype_code(q),
@@ -673,8 +740,12 @@ def attn_varlen_paged_fp8(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.T
                           seq_lens: torch.Tensor, cu_seqlens_q: torch.Tensor, k_scale: torch.Tensor | None = None,
                           v_scale: torch.Tensor | None = None, max_kv: int | None = None,
                           scale: float | None = None, causal: bool = True,
-                          out: torch.Tensor | None = None) -> torch.Tensor:
-    """attn_varlen_paged over 1-byte pools of fp8 e4m3fn codes; pools and scales as for attn_decode_paged_fp8."""
+                          out: torch.Tensor | None = None, workspace: torch.Tensor | None = None,
+                          split_keys: int = 0) -> torch.Tensor:
+    """attn_varlen_paged over 1-byte pools of fp8 e4m3fn codes; pools and scales as for attn_decode_paged_fp8;
+    workspace / split_keys as for attn_varlen_paged (pli_attn_varlen_paged_fp8_ws)."""
+    if workspace is not None:
+        _varlen_workspace("attn_varlen_paged_fp8", workspace, split_keys, q, k_pool, block_table, max_kv)
     dev = _check_varlen_fp8("attn_varlen_paged_fp8", q, k_pool, v_pool, k_scale, v_scale, block_table, seq_lens,
                             cu_seqlens_q)
     T, H, D = q.shape
@@ -698,6 +769,15 @@ def attn_varlen_paged_fp8(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.T
                                           v_pool.stride(0), v_pool.stride(1), v_pool.stride(2),
                                           out.stride(0), out.stride(1))))
     with _on_device(dev):
+        if workspace is not None:
+            rc = lib().pli_attn_varlen_paged_fp8_ws(_ptr(q), _ptr(k_pool), _ptr(v_pool), _ptr(out),
+                                                    _ptr(cu_seqlens_q), _ptr(block_table), _ptr(seq_lens),
+                                                    _ptr(k_scale), _ptr(v_scale), B, T, H, Hkv, D, bs, num_blocks,
+                                                    max_blocks, max_kv, st, float(scale), int(bool(causal)),
+                                                    _dtype_code(q), int(split_keys), _ptr(workspace),
+                                                    workspace.numel() * workspace.element_size(), _stream(dev))
+            _check(rc, "pli_attn_varlen_paged_fp8_ws")
+            return out
         rc = lib().pli_attn_varlen_paged_fp8(_ptr(q), _ptr(k_pool), _ptr(v_pool), _ptr(out), _ptr(cu_seqlens_q),
                                              _ptr(block_table), _ptr(seq_lens), _ptr(k_scale), _ptr(v_scale), B, T,
                                              H, Hkv, D, bs, num_blocks, max_blocks, max_kv, st, float(scale),
