@@ -625,6 +625,73 @@ int pli_attn_varlen_paged_fp8_ws(const void* q, const void* k_pool,
                                  void* workspace, size_t workspace_bytes,
                                  void* stream);
 
+/* Weight-only fp8 linear (W8A16) for decode batches: the weight stream of
+ * pli_gemv / pli_gemm NT / pli_gemm_swiglu at one byte per element.
+ *
+ * Weights: w8 [n, k] OCP fp8 e4m3fn codes (as the 1-byte KV pool above: 0x7E =
+ *   448, 0x7F / 0xFF NaN), row-major, leading dimension ldw in bytes
+ *   (= elements, >= k).  w_scale is device fp32 [n], one scale per output
+ *   row, read on the device (a captured call replays while codes and scales
+ *   change in place); NULL means all ones.  Element (j, i) has the value
+ *   decode(code) * w_scale[j].
+ * Result: C[r, j] = round_T( w_scale[j] * sum_i decode(w8[j, i]) * X[r, i]
+ *   (+ bias[j]) ), the sum in fp32 and one rounding to T.  T (dtype) is bf16
+ *   or fp16 and is the type of X, C and bias; PLI_F32 is refused.  Each code
+ *   is widened exactly to T on its way into the kernel and a code x 16-bit
+ *   product is exact in fp32, so the result is the 16-bit linear over the
+ *   dequantised weights with the scale folded in after the sum.  A NaN code
+ *   makes exactly the outputs of its row NaN.
+ * SwiGLU: h = silu(wg_scale[j] * sum g) * (wu_scale[j] * sum u), silu(g) =
+ *   g / (1 + e^-g) as pli_gemm_swiglu; neither gate nor up is written.
+ * Routes, in this order, from host arguments only (csrc/fp8w_plan.h;
+ *   pli_last_route names the kernels):
+ *   1. k == 0: C = bias or 0 ("linear_fp8w_generic"); m == 0 or n == 0:
+ *      nothing.
+ *   2. "linear_fp8w_smallm" (MFMA 16x16x32): 1 < m <= 128, k % 256 == 0,
+ *      n % 16 == 0, w8 / x / c 16-byte aligned, ldw % 16 == 0, ldx and ldc
+ *      % 8 == 0.
+ *   3. "linear_fp8w_vec" (VALU, one wave per 2 / 4 weight rows): m <= 16,
+ *      k % 16 == 0, ldw % 16 == 0, ldx % 8 == 0, w8 / x 16-byte aligned.
+ *      Its MACs are v_dot2 on the packed pairs (fp32 accumulate), so it
+ *      agrees with the other routes to fp32 rounding, not bitwise.
+ *   4. "fp8w_widen+<pli_gemm's route>": m > 16, no fast route, a workspace
+ *      given, and pli_gemm's vector class (k, n, ldx, ldc % 8 == 0, x / c
+ *      16-byte aligned, bias 8-byte aligned).  The codes are widened to
+ *      T(decode * scale) (one fp32 multiply, one rounding) into the
+ *      workspace, contiguous [n][k], and the existing pli_gemm (trans_b = 1)
+ *      or pli_gemm_swiglu (gate, then up at the next 16-byte boundary) runs
+ *      over them: the prefill path.
+ *   5. "linear_fp8w_generic": one thread per output, any shape, leading
+ *      dimension and alignment.
+ *   The SwiGLU kernels report "<name><swiglu>".
+ * Workspace: pli_linear_fp8w_workspace_size is 0 for m <= 16 and for
+ *   m <= 128 with k % 256 == 0 and n % 16 == 0 (a fast route takes aligned
+ *   operands), else n * k * 2 rounded up to 16 bytes; twice that for SwiGLU.
+ *   Caller-owned, 16-byte aligned scratch; nothing persists between calls.
+ *   Without one (NULL) such a shape takes the generic kernel.
+ * pli_gemv_fp8w: y[m] = w8[m, k] x, pli_linear_fp8w with one X row and no
+ *   bias on the same kernel, bitwise equal to it.
+ * PLI_EINVAL before any HIP call: a dtype other than fp16 / bf16, a negative
+ *   shape, a leading dimension below its width, a NULL operand of a
+ *   non-empty call, a misaligned or short workspace when route 4 would be
+ *   taken.  m == 0 or n == 0 returns PLI_OK and the operands may be NULL;
+ *   k == 0 writes bias or 0 and reads neither x nor the weights.  Nothing
+ *   is allocated or synchronised. */
+int pli_gemv_fp8w(const void* w8, const float* w_scale, const void* x, void* y,
+                  int m, int k, int64_t ldw, int dtype, void* stream);
+size_t pli_linear_fp8w_workspace_size(int m, int n, int k, int dtype);
+int pli_linear_fp8w(const void* x, const void* w8, const float* w_scale,
+                    const void* bias, void* c, int m, int n, int k,
+                    int64_t ldx, int64_t ldw, int64_t ldc, int dtype,
+                    void* workspace, size_t workspace_bytes, void* stream);
+size_t pli_linear_swiglu_fp8w_workspace_size(int m, int n, int k, int dtype);
+int pli_linear_swiglu_fp8w(const void* x, const void* wg8,
+                           const float* wg_scale, const void* wu8,
+                           const float* wu_scale, void* h, int m, int n, int k,
+                           int64_t ldx, int64_t ldwg, int64_t ldwu,
+                           int64_t ldh, int dtype, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------
  * Tuning section: the same operations with an explicit kernel choice, for
  * A/B runs (tools/tune.py) and the per-variant parity tests.  Not part of

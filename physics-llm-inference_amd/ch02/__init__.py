@@ -14,6 +14,7 @@ from .cached_generation import (
     SwiGLUFFN,
     cached_generate,
 )
+from .fp8_weight_model import Fp8Linear, Fp8WeightModel
 from .generation import naive_generate
 from .kv_cache import GQAWithCache, KVCache, attend_cached, calculate_kv_cache_size
 
@@ -30,4 +31,6 @@ __all__ = [
     "SwiGLUFFN",
     "naive_generate",
     "cached_generate",
+    "Fp8Linear",
+    "Fp8WeightModel",
 ]

@@ -6,7 +6,7 @@ from .batching_benchmark import (
     find_transition_batch_size,
 )
 from .gemm_benchmark import benchmark_gemm, gemm_bytes, gemm_flops
-from .gemv_benchmark import benchmark_gemv, gemv_bytes, gemv_flops
+from .gemv_benchmark import benchmark_gemv, benchmark_gemv_fp8w, gemv_bytes, gemv_flops, gemv_fp8w_bytes
 from .roofline import (
     MI355X,
     arithmetic_intensity,
@@ -22,6 +22,8 @@ __all__ = [
     "benchmark_gemv",
     "gemv_flops",
     "gemv_bytes",
+    "benchmark_gemv_fp8w",
+    "gemv_fp8w_bytes",
     "arithmetic_intensity",
     "roofline_throughput",
     "is_compute_bound",

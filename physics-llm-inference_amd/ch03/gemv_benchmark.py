@@ -103,6 +103,48 @@ def benchmark_gemv(
     return summarize(times, gemv_flops(m, k), gemv_bytes(m, k, dtype), kernel_us)
 
 
+def gemv_fp8w_bytes(m: int, k: int, dtype: torch.dtype = torch.bfloat16) -> int:
+    """Compulsory bytes with 1-byte weights: codes (m*k) + fp32 scales (4m) + x (2k) + y (2m)."""
+    return m * k + 4 * m + (k + m) * _elem(dtype)
+
+
+def benchmark_gemv_fp8w(
+    m: int,
+    k: int,
+    dtype: torch.dtype = torch.bfloat16,
+    warmup: int = 10,
+    iterations: int = 100,
+    device: str = "cuda",
+) -> BenchmarkResult:
+    """benchmark_gemv over e4m3 weights with one fp32 scale per row (``pli_gemv_fp8w``,
+    csrc/linear_fp8w.hip): the same method and fields, the fp8 byte count.  On the CPU the
+    dequantised torch.mv is timed instead."""
+    codes, scale = pli_hip.quantize_weight_fp8(torch.randn(m, k, dtype=torch.float32, device=device))
+    x = torch.randn(k, dtype=dtype, device=device)
+    on_gpu = codes.is_cuda
+    y = torch.empty(m, dtype=dtype, device=device)
+    weight = None if on_gpu else (codes.float() * scale[:, None]).to(dtype)
+
+    def call():
+        if on_gpu:
+            pli_hip.gemv_fp8w(codes, scale, x, out=y)
+        else:
+            torch.mv(weight, x)
+
+    for _ in range(warmup):
+        call()
+    _sync(device)
+    times = []
+    for _ in range(iterations):
+        _sync(device)
+        t0 = time.perf_counter()
+        call()
+        _sync(device)
+        times.append((time.perf_counter() - t0) * 1e6)
+    kernel_us = _event_time_us(call, iterations) if on_gpu else None
+    return summarize(times, gemv_flops(m, k), gemv_fp8w_bytes(m, k, dtype), kernel_us)
+
+
 def benchmark_decode_gemv(hidden_dim: int, dtype: torch.dtype = torch.float16) -> BenchmarkResult:
     return benchmark_gemv(hidden_dim, hidden_dim, dtype=dtype)
 

@@ -28,6 +28,14 @@ void clear_error() {
     g_route[0] = 0;
 }
 
+// An entry point that launched `first` and then called another entry point
+// (which started the route string anew): put `first` back in front.
+void route_prepend(const char* first) {
+    char rest[sizeof(g_route)];
+    snprintf(rest, sizeof(rest), "%s", g_route);
+    snprintf(g_route, sizeof(g_route), "%s%s%s", first, rest[0] ? "+" : "", rest);
+}
+
 // debug mode (PLI_SYNC=1 or HIP_LAUNCH_BLOCKING=1 in the environment, or
 // pli_debug_sync(1)): every
 // launch is followed by hipDeviceSynchronize + hipGetLastError, so a kernel

@@ -108,6 +108,14 @@ _SIGS = {
     "pli_attn_varlen_paged_fp8_ws": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int,
                                      _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_i64), _c_f32, _c_int,
                                      _c_int, _c_int, _vp, ctypes.c_size_t, _vp],
+    # weight-only fp8 linear (W8A16): codes + one fp32 scale per output row
+    "pli_gemv_fp8w": [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_i64, _c_int, _vp],
+    "pli_linear_fp8w_workspace_size": [_c_int] * 4,
+    "pli_linear_fp8w": [_vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_int, _vp,
+                        ctypes.c_size_t, _vp],
+    "pli_linear_swiglu_fp8w_workspace_size": [_c_int] * 4,
+    "pli_linear_swiglu_fp8w": [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_i64,
+                               _c_int, _vp, ctypes.c_size_t, _vp],
     # tuning entry points (include/pli.h tuning section): explicit kernel variant
     "pli_flash_attn_fwd_variant": [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int,
                                    _c_int, ctypes.POINTER(_c_i64), _c_f32, _c_int, _c_int, _vp,
@@ -1074,6 +1082,151 @@ def gemm_swiglu(x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor,
         else:
             rc = lib().pli_gemm_swiglu(*head, _stream(dev))
     _check(rc, "pli_gemm_swiglu")
+    return out
+
+
+# ------------------------------------------- weight-only fp8 linear (W8A16)
+FP8_E4M3_MAX = 448.0
+
+
+def quantize_weight_fp8(w: torch.Tensor, scale: torch.Tensor | None = None):
+    """Per-output-row e4m3fn quantisation of a weight [n, k] (torch ops only; CPU or GPU):
+    ``(codes, scale)`` with codes ``torch.float8_e4m3fn`` [n, k] and scale fp32 [n], value = code * scale[row].
+    scale[j] = absmax(row j) / 448 in fp32 (1.0 for an all-zero row), or the given ``scale``;
+    codes = (w.float() * (1.0f / scale)).clamp(-448, 448) cast to e4m3fn (round to nearest even): the rule of the
+    quantising KV appends.  Non-finite weights raise ``ValueError``."""
+    if w.dim() != 2:
+        raise ValueError(f"quantize_weight_fp8 expects a [n, k] weight, got {tuple(w.shape)}")
+    wf = w.detach().float()
+    if not bool(torch.isfinite(wf).all()):
+        raise ValueError("quantize_weight_fp8: non-finite weight")
+    n = wf.shape[0]
+    if scale is None:
+        amax = wf.abs().amax(dim=1) if wf.shape[1] else torch.zeros(n, dtype=torch.float32, device=wf.device)
+        scale = torch.where(amax > 0, amax / FP8_E4M3_MAX, torch.ones_like(amax))
+    else:
+        scale = scale.detach().to(device=wf.device, dtype=torch.float32)
+        if tuple(scale.shape) != (n,) or not bool((torch.isfinite(scale) & (scale > 0)).all()):
+            raise ValueError(f"quantize_weight_fp8: scale must be {n} finite positive values")
+    scale = scale.contiguous()
+    inv = 1.0 / scale
+    codes = (wf * inv[:, None]).clamp(-FP8_E4M3_MAX, FP8_E4M3_MAX).to(torch.float8_e4m3fn)
+    return codes, scale
+
+
+def _check_fp8w(what: str, x: torch.Tensor, weights) -> torch.device:
+    """x [m, k] fp16 / bf16 on a device; each (codes, scale): codes [n, k] float8_e4m3fn / uint8 with a unit column
+    stride, scale None or contiguous fp32 [n], all on x's device"""
+    dev = _require_gpu(x)
+    if x.dtype not in (torch.float16, torch.bfloat16):
+        raise PliError(f"{what}: activations must be fp16 or bf16, got {x.dtype}")
+    n = weights[0][0].shape[0] if weights[0][0].dim() == 2 else -1
+    for codes, scale in weights:
+        if not codes.is_cuda:
+            raise PliError("HIP path called with a CPU tensor")
+        if codes.device != dev or codes.dtype not in FP8_POOL_DTYPES:
+            raise PliError(f"{what}: codes must be a torch.float8_e4m3fn or torch.uint8 tensor on {dev}, "
+                           f"got {codes.dtype} on {codes.device}")
+        if codes.dim() != 2 or codes.shape[0] != n or codes.shape[1] != x.shape[-1]:
+            raise PliError(f"{what} shape mismatch: x{tuple(x.shape)} codes{tuple(codes.shape)}")
+        if codes.numel() and codes.stride(1) != 1:
+            raise PliError(f"{what}: codes need a unit column stride (they are used in place)")
+        if scale is not None and (not scale.is_cuda or scale.device != dev or scale.dtype != torch.float32 or
+                                  tuple(scale.shape) != (n,) or not scale.is_contiguous()):
+            raise PliError(f"{what}: scale must be None or a contiguous fp32 [{n}] tensor on {dev}")
+    return dev
+
+
+def _fp8w_workspace(what: str, workspace, dev):
+    if workspace is None:
+        return None, 0
+    if not workspace.is_cuda or workspace.device != dev or not workspace.is_contiguous():
+        raise PliError(f"{what}: workspace must be a contiguous tensor on {dev}")
+    return workspace.data_ptr(), workspace.numel() * workspace.element_size()
+
+
+def _ldw(codes: torch.Tensor) -> int:
+    return max(codes.stride(0), codes.shape[1]) if codes.shape[0] > 1 else codes.shape[1]
+
+
+def linear_fp8w_workspace_bytes(m: int, n: int, k: int, dtype: torch.dtype = torch.bfloat16,
+                                swiglu: bool = False) -> int:
+    """bytes of workspace linear_fp8w (linear_swiglu_fp8w with ``swiglu``) wants for [m, k] x [n, k]^T; 0: none"""
+    fn = lib().pli_linear_swiglu_fp8w_workspace_size if swiglu else lib().pli_linear_fp8w_workspace_size
+    return int(fn(int(m), int(n), int(k), DTYPE_CODE.get(dtype, -1)))
+
+
+def linear_fp8w(x: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor | None, bias: torch.Tensor | None = None,
+                out: torch.Tensor | None = None, workspace: torch.Tensor | None = None) -> torch.Tensor:
+    """C = x W^T (+ bias) over fp8 weights: x [m, k] fp16 / bf16, codes [n, k] e4m3fn (or uint8) used in place
+    (any row stride), scale fp32 [n] or None (ones); W = decode(codes) * scale[:, None].  ``workspace`` (bytes from
+    linear_fp8w_workspace_bytes) lets m > 16 shapes without a fast kernel run widen + the 16-bit GEMM."""
+    if x.dim() != 2:
+        raise PliError(f"linear_fp8w expects a 2-D x, got {tuple(x.shape)}")
+    dev = _check_fp8w("linear_fp8w", x, [(codes, scale)])
+    if x.stride(1) != 1:
+        x = x.contiguous()
+    m, k = x.shape
+    n = codes.shape[0]
+    if bias is not None:
+        _require_gpu(x, bias)
+        bias = bias.contiguous()
+        if tuple(bias.shape) != (n,):
+            raise PliError(f"bias must be [{n}]")
+    if out is None:
+        out = torch.empty((m, n), dtype=x.dtype, device=dev)
+    else:
+        _check_out(out, x, (m, n), "linear_fp8w")
+    wsp, wsb = _fp8w_workspace("linear_fp8w", workspace, dev)
+    with _on_device(dev):
+        rc = lib().pli_linear_fp8w(_ptr(x), _ptr(codes), _ptr(scale), _ptr(bias), _ptr(out), m, n, k,
+                                   max(x.stride(0), k) if m > 1 else k, _ldw(codes), max(out.stride(0), n),
+                                   _dtype_code(x), wsp, wsb, _stream(dev))
+    _check(rc, "pli_linear_fp8w")
+    return out
+
+
+def gemv_fp8w(codes: torch.Tensor, scale: torch.Tensor | None, x: torch.Tensor,
+              out: torch.Tensor | None = None) -> torch.Tensor:
+    """y = W x over fp8 weights (torch.mv semantics): codes [m, k], scale fp32 [m] or None, x [k] fp16 / bf16"""
+    if x.dim() != 1:
+        raise PliError(f"gemv_fp8w expects a 1-D x, got {tuple(x.shape)}")
+    dev = _check_fp8w("gemv_fp8w", x, [(codes, scale)])
+    x = x.contiguous()
+    m, k = codes.shape
+    if out is None:
+        out = torch.empty(m, dtype=x.dtype, device=dev)
+    else:
+        _check_out(out, x, (m,), "gemv_fp8w")
+    with _on_device(dev):
+        rc = lib().pli_gemv_fp8w(_ptr(codes), _ptr(scale), _ptr(x), _ptr(out), m, k, _ldw(codes), _dtype_code(x),
+                                 _stream(dev))
+    _check(rc, "pli_gemv_fp8w")
+    return out
+
+
+def linear_swiglu_fp8w(x: torch.Tensor, g_codes: torch.Tensor, g_scale: torch.Tensor | None, u_codes: torch.Tensor,
+                       u_scale: torch.Tensor | None, out: torch.Tensor | None = None,
+                       workspace: torch.Tensor | None = None) -> torch.Tensor:
+    """h = silu(x Wg^T) * (x Wu^T) over fp8 gate / up weights in one launch (neither gate nor up is written)"""
+    if x.dim() != 2:
+        raise PliError(f"linear_swiglu_fp8w expects a 2-D x, got {tuple(x.shape)}")
+    dev = _check_fp8w("linear_swiglu_fp8w", x, [(g_codes, g_scale), (u_codes, u_scale)])
+    if x.stride(1) != 1:
+        x = x.contiguous()
+    m, k = x.shape
+    n = g_codes.shape[0]
+    if out is None:
+        out = torch.empty((m, n), dtype=x.dtype, device=dev)
+    else:
+        _check_out(out, x, (m, n), "linear_swiglu_fp8w")
+    wsp, wsb = _fp8w_workspace("linear_swiglu_fp8w", workspace, dev)
+    with _on_device(dev):
+        rc = lib().pli_linear_swiglu_fp8w(_ptr(x), _ptr(g_codes), _ptr(g_scale), _ptr(u_codes), _ptr(u_scale),
+                                          _ptr(out), m, n, k, max(x.stride(0), k) if m > 1 else k, _ldw(g_codes),
+                                          _ldw(u_codes), max(out.stride(0), n), _dtype_code(x), wsp, wsb,
+                                          _stream(dev))
+    _check(rc, "pli_linear_swiglu_fp8w")
     return out
 
 
