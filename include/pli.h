@@ -335,7 +335,10 @@ int pli_gemm_multi_nt(const void* x, int64_t ldx, int m, int k,
  * -- bitwise the row pli_rmsnorm writes -- kept on chip; then the groups of
  * pli_gemm_multi_nt on y (w_up non-NULL: every group is SwiGLU,
  * silu(y.w) * (y.w_up), w_up rows with the same ldw).  1 <= m <= 4 rows,
- * k % 8 == 0, k <= 8192, bf16/fp16. */
+ * k % 8 == 0, k <= 8192, bf16/fp16.  A workgroup holds the m normalised rows
+ * in m * k * 2 + 16 bytes of LDS: 65552 at the largest shape (m = 4,
+ * k = 8192), inside the 163840 bytes a gfx950 workgroup may use, so every
+ * shape these rules accept is launched. */
 int pli_rms_gemm_nt(const void* a, int64_t lda, const void* residual, int64_t ldr,
                     const void* norm_weight, float eps, void* h_out, int64_t ldh, int m, int k,
                     int tokens_per_batch, const void* const* w, const void* const* w_up,

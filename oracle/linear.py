@@ -74,6 +74,19 @@ def rms_norm(x, weight, eps=1e-6, residual=None):
     return h / np.sqrt(np.mean(h * h, axis=-1, keepdims=True) + eps) * np.asarray(weight, np.float64)
 
 
+def rms_linear(x, norm_weight, eps, w, residual=None):
+    """rms_norm(x (+ residual)) W^T: a decode-step norm and the projection that
+    consumes it (``CachedTransformerModel.forward``: ``self.norm`` then
+    ``self.lm_head``; ``CachedAttention``: ``input_norm`` then q / k / v)."""
+    return linear(rms_norm(x, norm_weight, eps, residual), w)
+
+
+def rms_swiglu(x, norm_weight, eps, w_gate, w_up, residual=None):
+    """swiglu of rms_norm(x (+ residual)): ``post_attn_norm`` then the gate / up
+    product of the FFN (``CachedTransformerBlock.forward``)."""
+    return swiglu(rms_norm(x, norm_weight, eps, residual), w_gate, w_up)
+
+
 def moe_route(logits, top_k, normalize=True):
     """Router of ``ch09/moe_layer.py:24-33`` in float64: softmax, top-k
     (descending, ties to the lower index), optional renormalisation."""

@@ -315,6 +315,8 @@ class CachedTransformerModel(nn.Module):
             return False
         B, S, hd = x.shape
         at = self.layers[0].attn
+        # pli_rms_gemm_nt's rules (include/pli.h): 1 <= m <= 4 rows, k % 8 == 0, k <= 8192, i.e. at most
+        # 65536 bytes of rows in LDS (+ 16 static), which a gfx950 workgroup may use
         return (B * S <= 4 and hd % 8 == 0 and hd <= 8192 and B * S * hd * 2 <= 65536
                 and _device_len_ok_shape(x, S, at.num_heads, at.num_kv_heads, at.head_dim))
 

@@ -234,6 +234,8 @@ extern "C" int pli_rms_gemm_nt(const void* a, int64_t lda, const void* residual,
     }
     args.ngroups = ngroups;
     const dim3 grid((unsigned)cdiv(ntot, 4));
+    // y rows in dynamic LDS next to the 16 static bytes of red[]: at most 4 * 8192 * 2 + 16 = 65552
+    // bytes of gfx950's 163840 per workgroup (no opt-in is needed below the device's limit)
     const size_t lds = (size_t)m * k * 2;
     const int rpt = cdiv(k / 8, 256);
     hipStream_t s = (hipStream_t)stream;

@@ -1,5 +1,5 @@
 """GPU parity of pli_rmsnorm (RMSNorm, optionally with the residual add
-fused) against the f64 oracle.  Output tolerance: relative 2^-7 for 16-bit
+fused) against the f64 oracle.  Output tolerance, per element: 2^-7 for 16-bit
 storage (two roundings: the stored residual sum and the output), 1e-5 fp32;
 the fused h output must equal the torch add bit for bit."""
 from __future__ import annotations
@@ -39,7 +39,9 @@ def test_rmsnorm_vs_oracle(rows, n, dt, res):
     ref = rms_norm(x.double().cpu().numpy(), w.double().cpu().numpy(), 1e-6,
                    None if r is None else r.double().cpu().numpy())
     got = y.double().cpu().numpy()
-    assert np.abs(got - ref).max() <= TOL[dt] * (np.abs(ref).max() + 1)
+    # per element (a max-norm bound lets one wrong small element pass); the bound on the stored h and the other
+    # row lengths and layouts: tests/test_gpu_decode_step.py::test_rmsnorm_y_per_element
+    assert np.all(np.abs(got - ref) <= TOL[dt] * (np.abs(ref) + 1))
 
 
 def test_rmsnorm_module_on_gpu_matches_reference_formula():

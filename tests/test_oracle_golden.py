@@ -156,3 +156,24 @@ def test_stress_fixture_matches_inputs():
         ref = oatt.naive_attention(q, k, v)
         out = bf16_from_bits(g[f"{name}_ref_flash"]).astype(np.float64)
         assert np.isclose(np.abs(out - ref).max(), float(g[f"{name}_ref_err"]), rtol=1e-9, atol=0)
+
+
+def test_rms_linear_and_rms_swiglu_oracles_match_torch_f64():
+    """oracle.linear.rms_linear / rms_swiglu against a direct torch float64
+    evaluation of RMSNorm.forward (x / sqrt(mean(x^2) + eps) * weight) followed
+    by F.linear (and F.silu(gate) * up), with and without the residual add."""
+    import torch.nn.functional as F
+    from oracle import linear as olin
+    k, n = 72, 5
+    x, r = seeded_normal((3, k), 41).astype(np.float64), seeded_normal((3, k), 42).astype(np.float64)
+    g = 1 + 0.1 * seeded_normal((k,), 43).astype(np.float64)
+    w, wu = (seeded_normal((n, k), 44 + i).astype(np.float64) * k ** -0.5 for i in range(2))
+    tw, twu, tg = torch.from_numpy(w), torch.from_numpy(wu), torch.from_numpy(g)
+    for eps in (1e-6, 0.0, 0.5):
+        for res in (None, r):
+            h = torch.from_numpy(x if res is None else x + res)
+            y = h / torch.sqrt(torch.mean(h ** 2, dim=-1, keepdim=True) + eps) * tg
+            np.testing.assert_allclose(olin.rms_linear(x, g, eps, w, residual=res), F.linear(y, tw).numpy(),
+                                       rtol=1e-12, atol=1e-14)
+            np.testing.assert_allclose(olin.rms_swiglu(x, g, eps, w, wu, residual=res),
+                                       (F.silu(F.linear(y, tw)) * F.linear(y, twu)).numpy(), rtol=1e-12, atol=1e-14)
