@@ -278,8 +278,10 @@ int pli_rmsnorm(const void* x, const void* residual, const void* weight, void* y
  * pli_gemm_grouped: for every expert e, rows r in [offsets[e], offsets[e+1]):
  *   c[r] = x[gather[r]] W_e^T  (gather NULL = identity), or with wu_ptrs
  *   silu(x W1_e^T) * (x W3_e^T); w_ptrs / wu_ptrs are DEVICE arrays of the
- *   experts' [n, k] weight pointers; rows_bound >= every expert's row count.
- *   bf16/fp16, k % 128 == 0, n % 16 == 0.
+ *   experts' [n, k] weight pointers; rows_bound >= offsets[experts], the
+ *   number of sorted rows (a host value: it also bounds every expert's rows,
+ *   picks the kernel and sizes its grid; a smaller value leaves rows
+ *   unwritten); c holds rows_bound rows.  bf16/fp16, k % 128 == 0, n % 16 == 0.
  * pli_moe_combine: out[t] = sum_k weights[t, k] * y[pos[t, k]] (fp32 sum in k
  *   order).
  */

@@ -2371,8 +2371,12 @@ extern "C" int pli_gemm_f32out(const void* a, const void* b, float* c, int m, in
 
 // Grouped NT GEMM over experts (see gemm_grouped_nt): C[r] = X[gather[r]] W_e^T
 // (or silu(. W1_e^T) * (. W3_e^T) when wu_ptrs != NULL) for r in expert e's
-// row range [offsets[e], offsets[e+1]).  rows_bound (host) bounds every
-// expert's row count and sizes the per-workgroup batch groups.
+// row range [offsets[e], offsets[e+1]).  rows_bound (host): rows_bound >=
+// offsets[experts], the number of sorted rows (so it bounds every expert's
+// rows too; c holds that many rows).  It picks the route, sizes the
+// per-workgroup batch groups and the slab grid, and bounds the 256-row slots
+// of gemm_256g: sum_e cdiv(count_e, 256) <= cdiv(rows_bound, 256) + experts
+// holds for a bound on the total, not for a bound on one expert.
 static int grouped_dispatch(const void* x, const int32_t* gather, const void* const* w_ptrs,
                             const void* const* wu_ptrs, void* c, const int32_t* offsets,
                             int experts, int rows_bound, int n, int k, int64_t ldx, int64_t ldw,
@@ -2452,10 +2456,11 @@ static int grouped_dispatch(const void* x, const int32_t* gather, const void* co
         // 256-row tile per (expert, slot); decode sizes stay on the
         // weight-streaming kernel below
         const bool sw = wu_ptrs != nullptr;
-        const int slots = cdiv(rows_bound, G2M) + experts;
+        const int64_t slots64 = ((int64_t)rows_bound + G2M - 1) / G2M + experts;  // (no int overflow near 2^31 rows)
         const int tn = cdiv(n, sw ? 128 : G2N);
-        const int64_t nb = (int64_t)slots * tn;
+        const int64_t nb = slots64 * tn;
         PLI_REQUIRE(nb < (1ll << 31), "pli_gemm_grouped: grid too large");
+        const int slots = (int)slots64;
         const auto* Xg = (const uint16_t*)x;
         const auto* const* Wg = (const uint16_t* const*)w_ptrs;
         const auto* const* Wug = (const uint16_t* const*)wu_ptrs;

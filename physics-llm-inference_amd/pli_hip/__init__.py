@@ -853,7 +853,9 @@ def gemm_grouped(x: torch.Tensor, gather: torch.Tensor | None, w_table: torch.Te
                  offsets: torch.Tensor, rows: int, n: int, k: int, ldw: int,
                  wu_table: torch.Tensor | None = None, out: torch.Tensor | None = None,
                  variant: int | None = None) -> torch.Tensor:
-    """Per-expert NT GEMM over expert-sorted rows (see include/pli.h)."""
+    """Per-expert NT GEMM over expert-sorted rows (see include/pli.h).
+    `rows` is the host bound rows_bound >= offsets[experts], the number of sorted rows
+    (tokens * top_k after moe_route); `out`, if given, holds that many rows."""
     dev = _require_gpu(x)
     E = offsets.numel() - 1
     if out is None:

@@ -90,8 +90,13 @@ def weight_view(w: np.ndarray, dt: str, device, padded: bool) -> torch.Tensor:
 
 
 # ---------------------------------------------------------- guarded outputs
+GUARDED_DT = dict(TDT, fp32=torch.float32)  # what a Guarded may hold (the MoE router's weights are fp32)
+_BITS = {2: torch.int16, 4: torch.int32}
+
+
 def sentinel_bits(dt: str) -> int:
-    return int(torch.tensor([SENTINEL], dtype=TDT[dt]).view(torch.int16).item())
+    t = torch.tensor([SENTINEL], dtype=GUARDED_DT[dt])
+    return int(t.view(_BITS[t.element_size()]).item())
 
 
 class Guarded:
@@ -111,7 +116,7 @@ class Guarded:
             guard = max(64, 2 * max(self.strides))
         self.guard = -(-guard // 8) * 8
         self.dt = dt
-        self.buf = torch.full((2 * self.guard + span,), SENTINEL, dtype=TDT[dt], device=device)
+        self.buf = torch.full((2 * self.guard + span,), SENTINEL, dtype=GUARDED_DT[dt], device=device)
         self.view = self.buf.as_strided(self.shape, self.strides, self.guard)
 
     def stray_writes(self, *regions) -> torch.Tensor:
@@ -121,7 +126,7 @@ class Guarded:
         mv = mask.as_strided(self.shape, self.strides, self.guard)
         for sel in regions:
             sel(mv).fill_(True)
-        bad = (self.buf.view(torch.int16) != sentinel_bits(self.dt)) & ~mask
+        bad = (self.buf.view(_BITS[self.buf.element_size()]) != sentinel_bits(self.dt)) & ~mask
         return bad.nonzero().flatten()
 
 
