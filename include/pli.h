@@ -696,6 +696,53 @@ int pli_linear_swiglu_fp8w(const void* x, const void* wg8,
                            int64_t ldx, int64_t ldwg, int64_t ldwu,
                            int64_t ldh, int dtype, void* workspace,
                            size_t workspace_bytes, void* stream);
+/* pli_rms_gemm_nt_fp8w: pli_rms_gemm_nt over fp8 weights -- a decode-step
+ * RMSNorm fused into the W8A16 projection that consumes it, one launch
+ * (kernel "rms_gemm_fp8w": the norm phase of pli_rms_gemm_nt in front of the
+ * dot phase of "linear_fp8w_vec").
+ * Norm, groups, row offsets, capacity and h_out are pli_rms_gemm_nt's: rows
+ *   h = a (+ residual) (written to h_out if not NULL, once), y = h *
+ *   rsqrt(mean(h^2) + eps) * norm_weight -- bitwise the row pli_rmsnorm writes
+ *   -- kept on chip; 1..3 groups share y, group g stores row r = b *
+ *   tokens_per_batch + s of its n_g columns at
+ *     c_g + b * stride_batch_g + (s + *row_offset_g) * stride_token_g (+ col),
+ *   row_offset_g a device int32 or NULL (= 0); rows >= capacity_g are dropped.
+ *   Group widths are arbitrary (a wave's rows may straddle two groups).
+ *   h_out must not overlap a or residual: every workgroup reads both while
+ *   workgroup 0 writes h_out (the same holds for pli_rms_gemm_nt), and no
+ *   output may overlap an input.
+ * Codes and scales are pli_linear_fp8w's: w8[g] [n_g, k] e4m3fn codes, leading
+ *   dimension ldw_g bytes; w_scale[g] device fp32 [n_g], read on the device.
+ *   w_scale (the array) or any one entry may be NULL: all ones.  Column j of
+ *   group g is round_T( w_scale_g[j] * sum_i decode(w8_g[j, i]) * y[r, i] ),
+ *   the sum in fp32 with the v_dot2 MACs, chunk order and accumulate order of
+ *   "linear_fp8w_vec", so for m <= 4 the result is bitwise pli_rmsnorm followed
+ *   by pli_linear_fp8w (pli_linear_swiglu_fp8w) on its vec route.  A NaN code
+ *   makes exactly its output column NaN (in all m rows).
+ * wu8 non-NULL: every group is SwiGLU, silu(w_scale_g[j] sum g) *
+ *   (wu_scale_g[j] sum u), wu8[g] with the same ldw_g; wu_scale as w_scale.
+ * PLI_EINVAL with a message, before any HIP call, unless: 1 <= m <= 4 rows in
+ *   whole batches of tokens_per_batch; k > 0, k % 16 == 0, k <= 8192;
+ *   lda / ldr / ldh >= k and % 8 == 0; ldw_g >= k and % 16 == 0; a, residual,
+ *   h_out, norm_weight, w8_g and wu8_g 16-byte aligned; 1..3 groups, n_g > 0;
+ *   dtype bf16 or fp16; eps finite and >= 0; a, norm_weight, the arrays
+ *   w8 / c / n / ldw / stride_batch / stride_token / row_offset / capacity
+ *   and every w8_g, c_g (wu8_g with wu8) non-NULL.
+ * A workgroup holds the m normalised rows in m * k * 2 + 16 bytes of LDS: 65552
+ *   at the largest shape (m = 4, k = 8192), inside the 163840 bytes a gfx950
+ *   workgroup may use, so every shape these rules accept is launched.  No
+ *   workspace; nothing is allocated or synchronised; the call replays in a
+ *   captured graph while codes, scales and *row_offset_g change in place.
+ *   pli_last_route: "rms_gemm_fp8w" or "rms_gemm_fp8w<swiglu>". */
+int pli_rms_gemm_nt_fp8w(const void* a, int64_t lda, const void* residual, int64_t ldr,
+                         const void* norm_weight, float eps, void* h_out, int64_t ldh,
+                         int m, int k, int tokens_per_batch,
+                         const void* const* w8, const float* const* w_scale,
+                         const void* const* wu8, const float* const* wu_scale,
+                         void* const* c, const int* n, const int64_t* ldw,
+                         const int64_t* stride_batch, const int64_t* stride_token,
+                         const int32_t* const* row_offset, const int* capacity,
+                         int ngroups, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------
  * Tuning section: the same operations with an explicit kernel choice, for

@@ -12,11 +12,26 @@ On a ROCm device a layer is the wrapped model's unfused device sequence with
 the fp8 calls: ``pli_rmsnorm`` (+ residual) -> ``pli_linear_fp8w`` (packed qkv)
 -> cache append -> decode / prefill attention -> ``pli_linear_fp8w`` (o_proj)
 -> ``pli_rmsnorm`` (+ residual) -> ``pli_linear_swiglu_fp8w`` ->
-``pli_linear_fp8w`` (down).  Prompt-sized calls without a fast fp8 kernel go
-through the widen + GEMM route over one workspace, grown outside any capture.
-The fused decode launches (``pli_rms_gemm_nt``) have no fp8 form yet, so a
-layer is 7 launches against the 16-bit model's 5.  On the CPU the weights are
-dequantised and the wrapped model's own CPU math runs.
+``pli_linear_fp8w`` (down): 7 launches against the 16-bit model's 5.  Prompt-sized
+calls without a fast fp8 kernel go through the widen + GEMM route over one
+workspace, grown outside any capture.  On the CPU the weights are dequantised
+and the wrapped model's own CPU math runs.
+
+``from_model(model, fused_decode=True)`` takes the 16-bit model's fused decode
+step over the fp8 weights: a call that passes ``CachedTransformerModel``'s
+``_fused_decode_ok`` conditions (at most 4 rows, a device-resident cache
+length) and has ``hidden % 16 == 0`` runs, per layer, 5 launches --
+``pli_rms_gemm_nt_fp8w`` (input norm + the pending residual add + q / k / v
+over the row blocks of the packed codes and scales, k / v straight into the
+cache) -> ``pli_attn_decode_dev`` -> ``pli_linear_fp8w`` (o_proj) ->
+``pli_rms_gemm_nt_fp8w`` (post-attention norm + residual + gate / up / silu *
+mul) -> ``pli_linear_fp8w`` (down) -- and the final norm inside the ``lm_head``
+launch.  The fused launch is bitwise ``pli_rmsnorm`` followed by the vec route
+of ``pli_linear_fp8w``, so a batch-1 step gives the unfused path's logits bit
+for bit.  Every other call (prefill, more rows, no device length, the CPU)
+takes the path above; the default is ``fused_decode=False``, and it is the
+faster path wherever the two were measured (the fused step is
+level at batch 1 of the 0.85B shape and slower elsewhere).
 
 Build it from a model that already sits on its device: the quantised tensors
 are plain attributes, which ``Module.to`` does not move.
@@ -29,7 +44,7 @@ import torch.nn.functional as F
 
 import pli_hip
 
-from .cached_generation import CachedTransformerModel, LayerKVCache, RMSNorm, _device_len_ok
+from .cached_generation import CachedTransformerModel, LayerKVCache, RMSNorm, _device_len_ok, _device_len_ok_shape
 from .kv_cache import attend_cached
 
 
@@ -125,12 +140,40 @@ class Fp8Block(nn.Module):
                                        self.up.scale, workspace=ws)
         return h, self.down(g, ws).view(B, S, self.hidden_dim)
 
+    # ---- fused decode step (CachedTransformerBlock.decode_fused over the fp8 weights): 5 launches
+    def decode_fused(self, x: torch.Tensor, pending: torch.Tensor | None, cache: LayerKVCache
+                     ) -> tuple[torch.Tensor, torch.Tensor]:
+        B, S, hd = x.shape
+        nq, nk = self.num_heads * self.head_dim, self.num_kv_heads * self.head_dim
+        codes, scale = self.qkv.codes, self.qkv.scale
+        # q / k / v: row blocks of the packed codes and scales, used in place
+        wq, wk, wv = ((codes[a:b], scale[a:b]) for a, b in ((0, nq), (nq, nq + nk), (nq + nk, nq + 2 * nk)))
+        cache.reserve(S)
+        q = torch.empty(B, S, nq, device=x.device, dtype=x.dtype)
+        norm = self.input_norm
+        if pending is None:
+            pli_hip.rms_qkv_into_cache_fp8w(x, norm.weight, norm.eps, wq, wk, wv, q, cache.k, cache.v, cache.pos)
+        else:
+            h = torch.empty_like(x)
+            pli_hip.rms_qkv_into_cache_fp8w(pending, norm.weight, norm.eps, wq, wk, wv, q, cache.k, cache.v,
+                                            cache.pos, residual=x, h_out=h)
+            x = h
+        cache.seq_len += S
+        o = pli_hip.attn_decode_dev(q.view(B, S, self.num_heads, self.head_dim), cache.k, cache.v, cache.pos,
+                                    n_kv_add=S, causal=S > 1)
+        a = self.o_proj(o.reshape(B, S, hd))
+        h2 = torch.empty_like(x)
+        g = pli_hip.rms_swiglu_fp8w(a, self.post_attn_norm.weight, self.post_attn_norm.eps, self.gate.codes,
+                                    self.gate.scale, self.up.codes, self.up.scale, residual=x, h_out=h2)
+        return h2, self.down(g)
+
 
 class Fp8WeightModel(nn.Module):
     """See the module docstring.  Construct with ``from_model``."""
 
-    def __init__(self, model: CachedTransformerModel, pow2_scales: bool = False):
+    def __init__(self, model: CachedTransformerModel, pow2_scales: bool = False, fused_decode: bool = False):
         super().__init__()
+        self.fused_decode = bool(fused_decode)
         self.embed, self.norm = model.embed, model.norm
         self.layers = nn.ModuleList([Fp8Block(b, pow2_scales) for b in model.layers])
         self.lm_head = Fp8Linear(model.lm_head.weight, pow2_scales)
@@ -139,10 +182,23 @@ class Fp8WeightModel(nn.Module):
         self._ws: torch.Tensor | None = None
 
     @classmethod
-    def from_model(cls, model: CachedTransformerModel, pow2_scales: bool = False) -> "Fp8WeightModel":
+    def from_model(cls, model: CachedTransformerModel, pow2_scales: bool = False, fused_decode: bool = False
+                   ) -> "Fp8WeightModel":
         """``pow2_scales``: power-of-two row scales (a 16-bit model can then hold the identical dequantised
-        weights); default absmax / 448"""
-        return cls(model, pow2_scales)
+        weights); default absmax / 448.  ``fused_decode``: decode steps of at most 4 rows over a device-resident
+        cache length run the 5-launch layer of ``pli_rms_gemm_nt_fp8w`` (module docstring); default the
+        unfused 7-launch layer"""
+        return cls(model, pow2_scales, fused_decode)
+
+    # the 16-bit model's conditions over this model's layers (they carry num_heads / num_kv_heads / head_dim)
+    def _fused_decode_ok(self, x: torch.Tensor, caches) -> bool:
+        if not self.fused_decode or caches is None or caches[0].pos is None or not len(self.layers):
+            return False
+        B, S, hd = x.shape
+        b0 = self.layers[0]
+        # pli_rms_gemm_nt_fp8w's rules (include/pli.h): 1 <= m <= 4 rows, k % 16 == 0, k <= 8192
+        return (B * S <= 4 and hd % 16 == 0 and hd <= 8192 and B * S * hd * 2 <= 65536
+                and _device_len_ok_shape(x, S, b0.num_heads, b0.num_kv_heads, b0.head_dim))
 
     create_caches = CachedTransformerModel.create_caches
 
@@ -174,6 +230,13 @@ class Fp8WeightModel(nn.Module):
             for i, layer in enumerate(self.layers):
                 x = layer.forward_cpu(x, caches[i] if caches is not None else None)
             return self.lm_head(self.norm(x))
+        if self._fused_decode_ok(x, caches):
+            pending = None
+            for i, layer in enumerate(self.layers):
+                x, pending = layer.decode_fused(x, pending, caches[i])
+            caches[0].pos.add_(input_ids.shape[1])
+            return pli_hip.rms_linear_fp8w(pending, self.norm.weight, self.norm.eps, self.lm_head.codes,
+                                           self.lm_head.scale, residual=x)
         ws = self._workspace(x.shape[0] * x.shape[1], x.dtype, x.device)
         pending = None
         for i, layer in enumerate(self.layers):

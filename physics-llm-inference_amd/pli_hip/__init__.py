@@ -116,6 +116,9 @@ _SIGS = {
     "pli_linear_swiglu_fp8w_workspace_size": [_c_int] * 4,
     "pli_linear_swiglu_fp8w": [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_i64,
                                _c_int, _vp, ctypes.c_size_t, _vp],
+    # pli_rms_gemm_nt with (w8, w_scale, wu8, wu_scale) pointer arrays in place of (w, w_up)
+    "pli_rms_gemm_nt_fp8w": [_vp, _c_i64, _vp, _c_i64, _vp, _c_f32, _vp, _c_i64, _c_int, _c_int, _c_int,
+                             _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _vp],
     # tuning entry points (include/pli.h tuning section): explicit kernel variant
     "pli_flash_attn_fwd_variant": [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int,
                                    _c_int, ctypes.POINTER(_c_i64), _c_f32, _c_int, _c_int, _vp,
@@ -1230,6 +1233,99 @@ def linear_swiglu_fp8w(x: torch.Tensor, g_codes: torch.Tensor, g_scale: torch.Te
                                           _stream(dev))
     _check(rc, "pli_linear_swiglu_fp8w")
     return out
+
+
+def _rms_gemm_fp8w(a: torch.Tensor, norm_weight: torch.Tensor, eps: float, groups: list,
+                   residual: torch.Tensor | None, h_out: torch.Tensor | None, tokens_per_batch: int,
+                   swiglu: bool) -> None:
+    """pli_rms_gemm_nt_fp8w.  groups: ((codes, scale), (up codes, up scale) | None, c, stride_batch,
+    stride_token, pos | None, capacity) with c the output base tensor."""
+    dev = _require_gpu(a, norm_weight)
+    a2 = _rows(a)
+    r2 = _rows(residual) if residual is not None else None
+    if r2 is not None:
+        _require_gpu(a2, r2)
+    if h_out is not None and (h_out.stride(-1) != 1 or tuple(h_out.shape[-1:]) != (a2.shape[1],)):
+        raise PliError("h_out must have unit inner stride and the hidden width")
+    h2 = h_out.view(-1, h_out.shape[-1]) if h_out is not None else None
+    m, k = a2.shape
+    for g in groups:
+        _check_fp8w("rms_gemm_fp8w", a2, [g[0]] + ([g[1]] if swiglu else []))
+        if swiglu and g[1][0].shape[0] > 1 and g[0][0].shape[0] > 1 and g[1][0].stride(0) != g[0][0].stride(0):
+            raise PliError("rms_gemm_fp8w: the up codes need the gate codes' row stride")
+        _require_gpu(a2, g[2])
+    ng = len(groups)
+    P = ctypes.c_void_p
+    w = (P * ng)(*(g[0][0].data_ptr() for g in groups))
+    ws = (P * ng)(*(_ptr(g[0][1]) for g in groups))
+    wu = (P * ng)(*(g[1][0].data_ptr() for g in groups)) if swiglu else None
+    wus = (P * ng)(*(_ptr(g[1][1]) for g in groups)) if swiglu else None
+    c = (P * ng)(*(g[2].data_ptr() for g in groups))
+    n = (_c_int * ng)(*(int(g[0][0].shape[0]) for g in groups))
+    ldw = (_c_i64 * ng)(*(_ldw(g[0][0]) for g in groups))
+    sb = (_c_i64 * ng)(*(int(g[3]) for g in groups))
+    stok = (_c_i64 * ng)(*(int(g[4]) for g in groups))
+    ro = (P * ng)(*(_ptr(g[5]) for g in groups))
+    cap = (_c_int * ng)(*(int(g[6]) for g in groups))
+    with _on_device(dev):
+        rc = lib().pli_rms_gemm_nt_fp8w(_ptr(a2), a2.stride(0), _ptr(r2), r2.stride(0) if r2 is not None else 0,
+                                        _ptr(norm_weight), float(eps), _ptr(h2),
+                                        h2.stride(0) if h2 is not None else 0, m, k, int(tokens_per_batch),
+                                        w, ws, wu, wus, c, n, ldw, sb, stok, ro, cap, ng, _dtype_code(a),
+                                        _stream(dev))
+    _check(rc, "pli_rms_gemm_nt_fp8w")
+
+
+def rms_linear_fp8w(a: torch.Tensor, norm_weight: torch.Tensor, eps: float, codes: torch.Tensor,
+                    scale: torch.Tensor | None, residual: torch.Tensor | None = None,
+                    h_out: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """rmsnorm(a (+ residual)) @ W^T over fp8 weights in one launch (decode: <= 4 rows); codes [n, k] e4m3fn or
+    uint8 used in place (any row stride % 16 == 0), scale fp32 [n] or None (ones)."""
+    a2 = a.reshape(-1, a.shape[-1])
+    n = codes.shape[0]
+    if out is None:
+        out = torch.empty(a2.shape[0], n, device=a.device, dtype=a.dtype)
+    # one token per "batch": row bb lands at out + bb * stride(0)
+    _rms_gemm_fp8w(a, norm_weight, eps, [((codes, scale), None, out, out.stride(0), 0, None, 1 << 30)],
+                   residual, h_out, 1, False)
+    return out.view(*a.shape[:-1], n)
+
+
+def rms_swiglu_fp8w(a: torch.Tensor, norm_weight: torch.Tensor, eps: float, g_codes: torch.Tensor,
+                    g_scale: torch.Tensor | None, u_codes: torch.Tensor, u_scale: torch.Tensor | None,
+                    residual: torch.Tensor | None = None, h_out: torch.Tensor | None = None,
+                    out: torch.Tensor | None = None) -> torch.Tensor:
+    """silu(y Wg^T) * (y Wu^T) with y = rmsnorm(a (+ residual)) over fp8 gate / up weights, one launch."""
+    a2 = a.reshape(-1, a.shape[-1])
+    n = g_codes.shape[0]
+    if out is None:
+        out = torch.empty(a2.shape[0], n, device=a.device, dtype=a.dtype)
+    _rms_gemm_fp8w(a, norm_weight, eps,
+                   [((g_codes, g_scale), (u_codes, u_scale), out, out.stride(0), 0, None, 1 << 30)],
+                   residual, h_out, 1, True)
+    return out.view(*a.shape[:-1], n)
+
+
+def rms_qkv_into_cache_fp8w(a: torch.Tensor, norm_weight: torch.Tensor, eps: float, q: tuple, k: tuple, v: tuple,
+                            q_out: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos: torch.Tensor,
+                            residual: torch.Tensor | None = None,
+                            h_out: torch.Tensor | None = None) -> torch.Tensor:
+    """rms_qkv_into_cache over fp8 weights, one launch; a [B, S, hidden]; q / k / v are (codes, scale) pairs
+    (row blocks of one packed [Wq; Wk; Wv] serve as they are)."""
+    B, S, _ = a.shape
+    S_max, Hkv, D = k_cache.shape[1:]
+    if pos.dtype != torch.int32 or not pos.is_cuda:
+        raise PliError("pos must be an int32 device tensor")
+    for t in (k_cache, v_cache):
+        if t.shape[0] != B or t.stride(3) != 1 or t.stride(2) != D:
+            raise PliError("caches must be [B, S_max, Hkv, D] with contiguous (Hkv, D) rows")
+    if q_out.dim() != 3 or tuple(q_out.shape[:2]) != (B, S) or q_out.stride(2) != 1:
+        raise PliError("q_out must be [B, S, Hq*D] with unit inner stride")
+    groups = [(q, None, q_out, q_out.stride(0), q_out.stride(1), None, S),
+              (k, None, k_cache, k_cache.stride(0), k_cache.stride(1), pos, S_max),
+              (v, None, v_cache, v_cache.stride(0), v_cache.stride(1), pos, S_max)]
+    _rms_gemm_fp8w(a, norm_weight, eps, groups, residual, h_out, S, False)
+    return q_out
 
 
 # ---------------------------------------------------------------------- GEMV
