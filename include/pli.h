@@ -282,6 +282,10 @@ int pli_rmsnorm(const void* x, const void* residual, const void* weight, void* y
  *   number of sorted rows (a host value: it also bounds every expert's rows,
  *   picks the kernel and sizes its grid; a smaller value leaves rows
  *   unwritten); c holds rows_bound rows.  bf16/fp16, k % 128 == 0, n % 16 == 0.
+ *   Any number of experts the grid of the chosen kernel holds: the LDS-staged
+ *   kernel (16 < rows_bound <= 1024) indexes experts in blockIdx.z and is
+ *   chosen only for experts <= 65535; beyond that the weight-streaming and
+ *   256-row-tile kernels run ("grid too large" past 2^31 workgroups).
  * pli_moe_combine: out[t] = sum_k weights[t, k] * y[pos[t, k]] (fp32 sum in k
  *   order).
  */
@@ -795,7 +799,8 @@ int pli_rms_gemm_nt_fp8w(const void* a, int64_t lda, const void* residual, int64
  *   route applies, 2 never split, 3 gemm_w5's SwiGLU tile (the prefill
  *   default), 4 the phased 256 x 128 tile (3 and 4 never split).
  * pli_gemm_grouped_variant: 0 default, 1/2 alternate routes (gemm.hip
- *   grouped_dispatch).
+ *   grouped_dispatch); 2, the LDS-staged kernel wherever it applies, is an
+ *   argument error with more than 65535 experts.
  */
 int pli_flash_attn_fwd_variant(const void* q, const void* k, const void* v, void* o, int batch,
                                int heads, int kv_heads, int n_q, int n_kv, int head_dim,

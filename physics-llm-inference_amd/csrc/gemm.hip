@@ -2377,6 +2377,9 @@ extern "C" int pli_gemm_f32out(const void* a, const void* b, float* c, int m, in
 // per-workgroup batch groups and the slab grid, and bounds the 256-row slots
 // of gemm_256g: sum_e cdiv(count_e, 256) <= cdiv(rows_bound, 256) + experts
 // holds for a bound on the total, not for a bound on one expert.
+// The LDS-staged route puts the expert in blockIdx.z (at most 65535): with
+// more experts the default takes the routes below it, which index experts in
+// blockIdx.x and guard their own grids, and variant 2 is an argument error.
 static int grouped_dispatch(const void* x, const int32_t* gather, const void* const* w_ptrs,
                             const void* const* wu_ptrs, void* c, const int32_t* offsets,
                             int experts, int rows_bound, int n, int k, int64_t ldx, int64_t ldw,
@@ -2426,7 +2429,10 @@ static int grouped_dispatch(const void* x, const int32_t* gather, const void* co
     // (1 token: 140 vs 312 us).
     const bool sw = wu_ptrs != nullptr;
     const bool lds_ok = rows_bound <= 1024 && n % (sw ? 64 : 128) == 0;
-    if (lds_ok && variant != 1 && (variant == 2 || rows_bound > 16)) {
+    // the expert is blockIdx.z there: a grid dimension the hardware limits to 65535
+    PLI_REQUIRE(!(variant == 2 && lds_ok) || experts <= 65535,
+                "pli_gemm_grouped: the LDS-staged route takes at most 65535 experts (E=%d)", experts);
+    if (lds_ok && experts <= 65535 && variant != 1 && (variant == 2 || rows_bound > 16)) {
         const int mc = cdiv(min(rows_bound, 128), 32);
         const dim3 grid((unsigned)(n / (sw ? 64 : 128)), (unsigned)cdiv(rows_bound, 128), (unsigned)experts);
         const auto* Xg = (const uint16_t*)x;

@@ -68,10 +68,14 @@ def synthetic_routing(counts, tokens: int, seed: int):
 
 
 def grouped_route(E: int, rows_bound: int, n: int, swiglu: bool, variant) -> str:
-    """the kernel instance grouped_dispatch (csrc/gemm.hip) launches; variant None = pli_gemm_grouped"""
+    """the kernel instance grouped_dispatch (csrc/gemm.hip) launches; variant None = pli_gemm_grouped.  The
+    LDS-staged kernel indexes experts in blockIdx.z: past 65535 experts the default leaves it and variant 2, where
+    it would have run, is an argument error (ValueError here)"""
     v, sw = variant or 0, int(bool(swiglu))
     lds_ok = rows_bound <= 1024 and n % (64 if swiglu else 128) == 0
-    if lds_ok and v != 1 and (v == 2 or rows_bound > 16):
+    if lds_ok and v == 2 and E > 65535:
+        raise ValueError("the LDS-staged route takes at most 65535 experts (blockIdx.z)")
+    if lds_ok and E <= 65535 and v != 1 and (v == 2 or rows_bound > 16):
         return f"gemm_grouped_lds_nt<MC{cdiv(min(rows_bound, 128), 32)},SW{sw}>"
     if v != 2 and rows_bound >= 16 * E:
         return f"gemm_256g<SW{sw}>"

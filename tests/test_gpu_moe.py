@@ -25,7 +25,10 @@ padding of the logits):
     gemm_256g<T, SW 0/1>                          255 / 256 / 257 / 1 rows,
       ragged last column tile, (1100, 1100) at rows_bound 2200
   in bf16 and fp16.  No bitwise equality between routes is asserted: the
-  kernels' comments claim none.
+  kernels' comments claim none.  One more case has 65536 experts, more than
+  blockIdx.z of the LDS-staged kernel holds: the dispatch takes the
+  weight-streaming kernel, every empty expert's table entry names one NaN
+  weight.
 * the chain W1/W3 -> W2 -> combine: each stage against its own float64
   reference on the previous stage's stored output.
 * router, through the C ABI (ld_logits > experts, NaN padding), for
@@ -186,6 +189,48 @@ def test_grouped_routes_each_meet_the_oracle(c, dt):
     """one shape under variant None / 1 / 2 (two different kernels): each is held to the oracle on its own"""
     op, out = _run_grouped(c, dt)
     _check_rows(out, mc.grouped_reference(op), dt, f"{mc.grouped_id(c)} {dt}")
+
+
+@pytest.mark.parametrize("dt", dc.DTYPES)
+@pytest.mark.parametrize("sw", [False, True], ids=["plain", "swiglu"])
+def test_grouped_gemm_with_more_experts_than_grid_z(sw, dt):
+    """E = 65536, rows only in experts 0, 40000 and 65535 (5, 9, 6): the LDS-staged kernel would need blockIdx.z =
+    65535 + 1, so the dispatch takes the weight-streaming kernel.  Every empty expert's table entry names one NaN
+    weight; the output is held per element like the other grouped cases."""
+    import pli_hip
+    E, n, k, live = 65536, 128, 128, {0: 5, 40000: 9, 65535: 6}
+    rows = sum(live.values())
+    assert mc.grouped_route(E, rows, n, sw, None) == f"gemm_grouped_nt<NBG2,SW{int(sw)}>"
+    seed = 4000 + (500 if dt == "fp16" else 0) + int(sw)
+    tokens = max(live.values()) + 3
+    compact, gather = mc.synthetic_routing(list(live.values()), tokens, seed)
+    x = round_to_dtype(seeded_normal((tokens, k), seed + 1), dt)
+    used = np.zeros(tokens, bool)
+    used[gather] = True
+    x[~used] = np.nan
+    wgt = lambda s: round_to_dtype(seeded_normal((n, k), s) * np.float32(k ** -0.5), dt)  # noqa: E731
+    w = [wgt(seed + 10 + i) for i in range(3)]
+    wu = [wgt(seed + 110 + i) for i in range(3)] if sw else None
+    op = mc.GroupedOperands(x, w, wu, gather, compact, tokens)
+    counts = np.zeros(E, np.int64)
+    counts[list(live)] = list(live.values())
+    offsets = torch.from_numpy(np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)).to(DEV)
+
+    def table(ws):
+        dead = dc.weight_view(np.full((n, k), np.nan, np.float32), dt, DEV, True)
+        held = [dc.weight_view(a, dt, DEV, True) for a in ws]
+        t = torch.full((E,), dead.data_ptr(), dtype=torch.int64)
+        t[list(live)] = torch.tensor([h.data_ptr() for h in held], dtype=torch.int64)
+        return t.to(DEV), held + [dead]
+
+    wt, keep = table(w)
+    wut, keep_u = table(wu) if sw else (None, None)
+    out = dc.Guarded((rows + 3, n), dt, DEV, strides=(n + 8, 1))
+    pli_hip.gemm_grouped(dc.row_view(x, dt, DEV, 8), torch.from_numpy(gather).to(DEV), wt, offsets, rows, n, k,
+                         keep[0].stride(0), wu_table=wut, out=out.view)
+    assert pli_hip.last_route() == LAUNCH_NAME["gemm_grouped_nt"], pli_hip.last_route()
+    torch.cuda.synchronize()
+    _check_rows(out, mc.grouped_reference(op), dt, f"E65536 {'swiglu' if sw else 'plain'} {dt}")
 
 
 def _combine_checked(y, pos, w, T, K, H, padded, dt, what):

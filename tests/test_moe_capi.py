@@ -126,6 +126,33 @@ def test_gemm_grouped_grid_guards_without_gpu(L):
     assert L.pli_last_route() == b""
 
 
+def test_gemm_grouped_lds_route_refuses_more_experts_than_grid_z_without_gpu(L):
+    """the LDS-staged kernel indexes experts in blockIdx.z (<= 65535): forcing it (variant 2) with more experts is
+    an argument error wherever it would have run; 65535 experts and the shapes it never took pass this rule (the
+    replay of tests/moe_cases.py says the same); pli.h and the comment above grouped_dispatch state the limit"""
+    import moe_cases as mc
+    err = L.pli_last_error
+    for kw in (dict(rows=8, n=128, ldc=128), dict(rows=20, n=128, ldc=128), dict(rows=1024, n=256, ldc=256),
+               dict(rows=20, n=64, wu=P), dict(rows=1024, n=128, wu=P, ldc=128)):
+        for E in (65536, 1 << 20):
+            assert _grouped(L, 2, experts=E, **kw) == EINVAL, (kw, E)
+            assert b"pli_gemm_grouped: the LDS-staged route takes at most 65535 experts (E=%d)" % E in err()
+            with pytest.raises(ValueError):
+                mc.grouped_route(E, kw["rows"], kw["n"], "wu" in kw, 2)
+    # (where the route does not apply, variant 2 falls through as before: here onto the next rule)
+    assert _grouped(L, 2, experts=1 << 20, rows=2048, n=32768, ldc=32768) == EINVAL and b"grid too large" in err()
+    assert mc.grouped_route(1 << 20, 2048, 32768, False, 2) == "gemm_grouped_nt<NBG8,SW0>"
+    # the default leaves the LDS route at 65536 experts, for the weight-streaming kernel
+    assert mc.grouped_route(65535, 20, 128, False, None) == "gemm_grouped_lds_nt<MC1,SW0>"
+    assert mc.grouped_route(65536, 20, 128, False, None) == "gemm_grouped_nt<NBG2,SW0>"
+    assert mc.grouped_route(65536, 20, 128, True, None) == "gemm_grouped_nt<NBG2,SW1>"
+    assert L.pli_last_route() == b""
+    header = " ".join(open(os.path.join(ROOT, "include", "pli.h")).read().split())
+    src = open(os.path.join(PKG, "csrc", "gemm.hip")).read()
+    com = " ".join(src[src.index("// Grouped NT GEMM over experts"):src.index("static int grouped_dispatch(")].split())
+    assert "blockIdx.z" in com and "65535" in com and "chosen only for experts <= 65535" in header
+
+
 def test_rows_bound_contract_reads_the_same_everywhere():
     """rows_bound >= offsets[experts], the number of sorted rows (which also bounds every expert): pli.h, the comment
     above grouped_dispatch and pli_hip.gemm_grouped.  gemm_256g's grid is cdiv(rows_bound, 256) + experts slots,
