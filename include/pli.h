@@ -748,6 +748,48 @@ int pli_rms_gemm_nt_fp8w(const void* a, int64_t lda, const void* residual, int64
                          const int32_t* const* row_offset, const int* capacity,
                          int ngroups, int dtype, void* stream);
 
+/* Next-token sampling on the device: temperature, top-k, top-p and the draw of
+ * ch02/generation.py:23-31 (temperature, top-k, multinomial),
+ * ch02/cached_generation.py:245,265 (temperature) and ch10/engine.py:96-115
+ * (greedy at temperature 0, top-p, multinomial) in one launch, one workgroup
+ * per row of `vocab` logits.  The rule, per row (DESIGN.md "Sampling" has it in
+ * full; csrc/sample_plan.h is its host-replayable part):
+ *   NaN counts as -inf and -0 as +0.  No logit above -inf: token -1.  With a
+ *   +inf in the row the +inf logits weigh 1 and all others 0.  "Before" means
+ *   larger value first, lower index first among equal values (comparisons on
+ *   integer keys, never arithmetic).  temperature == 0: the first token
+ *   (argmax, lowest index on ties); top_k, top_p and the uniform are ignored.
+ *   Otherwise K1 = the first top_k tokens (top_k <= 0 or >= vocab: all),
+ *   w_i = exp((x_i - max) / temperature), S1 = sum over K1; token i of K1 is
+ *   kept iff the weight of the K1 tokens before it is <= top_p * S1 (the first
+ *   always; top_p >= 1: all of K1); the draw walks the kept tokens in
+ *   ascending index and takes the first whose running sum exceeds u * S2.
+ *   Weights are held as integers, floor(w * 2^45): every sum is exact and
+ *   order-free, so the same inputs give the same token on every call and
+ *   every replay.
+ * u: uniforms[row] (device fp32 [rows], each in [0, 1)) when uniforms is not
+ *   NULL; else (r0 >> 8) * 2^-24, r0 the first word of Philox4x32-10 with key
+ *   {seed & 0xffffffff, seed >> 32} and counter {(uint32)offset, row, 0, 0},
+ *   offset = (offset_dev ? *offset_dev : 0) + offset_add.  offset_dev is read
+ *   by the kernel: a captured call replays while it changes in place.
+ * logits [rows, vocab] of dtype (fp32 / fp16 / bf16), leading dimension
+ *   ld_logits >= vocab elements, any alignment.  tokens: int64, row r at
+ *   tokens[r * ld_tokens], ld_tokens >= 1.  vocab <= 262144 (2^18 weights of
+ *   at most 2^45 sum below 2^64); above it PLI_EUNSUPPORTED.
+ * Workspace: pli_sample_workspace_size is 0 (the state is in LDS); workspace
+ *   may be NULL, a non-NULL one must be 16-byte aligned.
+ * PLI_EINVAL before any HIP call: rows < 0, vocab < 1, ld_logits < vocab,
+ *   ld_tokens < 1, a bad dtype, a negative or NaN temperature or top_p, a
+ *   misaligned workspace, NULL logits or tokens when rows > 0.  rows == 0 does
+ *   nothing and returns PLI_OK.  Nothing is allocated or synchronised.
+ * pli_last_route: "sample_greedy" (temperature == 0) or "sample_select". */
+size_t pli_sample_workspace_size(int rows, int vocab, int dtype);
+int pli_sample(const void* logits, int64_t ld_logits, int rows, int vocab, int dtype,
+               float temperature, int top_k, float top_p, const float* uniforms,
+               uint64_t seed, const int32_t* offset_dev, int64_t offset_add,
+               int64_t* tokens, int64_t ld_tokens, void* workspace,
+               size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------
  * Tuning section: the same operations with an explicit kernel choice, for
  * A/B runs (tools/tune.py) and the per-variant parity tests.  Not part of

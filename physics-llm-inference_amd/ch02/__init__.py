@@ -16,6 +16,7 @@ from .cached_generation import (
 )
 from .fp8_weight_model import Fp8Linear, Fp8WeightModel
 from .generation import naive_generate
+from .sampling import Sampler, sample_cpu
 from .kv_cache import GQAWithCache, KVCache, attend_cached, calculate_kv_cache_size
 
 __all__ = [
@@ -33,4 +34,6 @@ __all__ = [
     "cached_generate",
     "Fp8Linear",
     "Fp8WeightModel",
+    "Sampler",
+    "sample_cpu",
 ]

@@ -337,10 +337,14 @@ def _sync(device: torch.device) -> None:
 
 
 def cached_generate(model: CachedTransformerModel, input_ids: torch.Tensor, max_new_tokens: int,
-                    temperature: float = 1.0) -> tuple[torch.Tensor, dict]:
+                    temperature: float = 1.0, sampler=None) -> tuple[torch.Tensor, dict]:
     """Prefill the prompt once, then decode one token per step over the caches
     (``ch02/cached_generation.py:204-274``).  Returns the prompt followed by
-    the sampled tokens, and {prefill_ms, decode_ms[], total_ms}."""
+    the sampled tokens, and {prefill_ms, decode_ms[], total_ms}.  ``sampler``
+    (this build; a ``ch02.Sampler``) replaces the softmax / multinomial chain
+    (and ``temperature``) with one call per token, the token at sequence
+    position p drawn with offset p: the sequence is then a function of the
+    sampler's seed.  None is the reference's path."""
     model.eval()
     device = input_ids.device
     dtype = next(model.parameters()).dtype
@@ -349,7 +353,9 @@ def cached_generate(model: CachedTransformerModel, input_ids: torch.Tensor, max_
     timings = {"prefill_ms": 0, "decode_ms": [], "total_ms": 0}
     out = [input_ids]
 
-    def sample(logits):
+    def sample(logits, pos=0):
+        if sampler is not None:
+            return sampler(logits[:, -1, :], pos).view(-1, 1)
         probs = F.softmax(logits[:, -1, :] / temperature, dim=-1)
         return torch.multinomial(probs, num_samples=1)
 
@@ -359,7 +365,7 @@ def cached_generate(model: CachedTransformerModel, input_ids: torch.Tensor, max_
         logits = model(input_ids, caches, start_pos=0)
         _sync(device)
         timings["prefill_ms"] = (time.perf_counter() - t0) * 1000
-        token = sample(logits)
+        token = sample(logits, prompt_len)
         out.append(token)
         for i in range(max_new_tokens - 1):
             _sync(device)
@@ -367,7 +373,7 @@ def cached_generate(model: CachedTransformerModel, input_ids: torch.Tensor, max_
             logits = model(token, caches, start_pos=prompt_len + i)
             _sync(device)
             timings["decode_ms"].append((time.perf_counter() - t0) * 1000)
-            token = sample(logits)
+            token = sample(logits, prompt_len + i + 1)
             out.append(token)
 
     timings["total_ms"] = timings["prefill_ms"] + sum(timings["decode_ms"])

@@ -86,11 +86,25 @@ class DecodeStepGraph:
 
     ``step`` returns the static logits buffer [B, 1, vocab] (overwritten by the
     next step; clone to keep it).
+
+    With ``sampler`` (a ``ch02.Sampler``) the token choice is in the graph too:
+    the capture records the model step and then, last, one ``pli_sample``
+    launch that reads ``static_logits[:, -1]``, takes its random-number offset
+    from the device-resident cache length (already advanced by the step, so the
+    token at sequence position p is drawn with offset p) and writes the ids
+    straight into ``static_ids``, the next replay's input:
+
+        g = DecodeStepGraph(model, 8, 4096, torch.bfloat16, sampler=Sampler(0.8, top_k=50, seed=1))
+        g.prefill(prompt_ids, sample=True)       # eager; draws the first token
+        ids = g.generate(n)                      # [B, n]: n graph launches, nothing else
+
+    ``sampler=None`` (the default) is the class as it was.
     """
 
     def __init__(self, model, batch_size: int, max_seq_len: int, dtype: torch.dtype,
-                 device: torch.device | str = "cuda", warmup: int = 2):
+                 device: torch.device | str = "cuda", warmup: int = 2, sampler=None):
         self.model = model
+        self.sampler = sampler
         self.caches = model.create_caches(batch_size, max_seq_len, torch.device(device), dtype,
                                           device_pos=True)
         self.pos = self.caches[0].pos
@@ -109,10 +123,14 @@ class DecodeStepGraph:
         self.pos.fill_(n)
 
     @torch.no_grad()
-    def prefill(self, input_ids: torch.Tensor) -> torch.Tensor:
+    def prefill(self, input_ids: torch.Tensor, sample: bool = False) -> torch.Tensor:
         logits = self.model(input_ids, self.caches, start_pos=self.seq_len)
         if self.graph is None:
             self._capture()
+        if sample:  # the first token, eagerly, from the same stream of random numbers: offset = its position
+            if self.sampler is None:
+                raise RuntimeError("DecodeStepGraph.prefill(sample=True) without a sampler")
+            self.sampler(logits[:, -1], self.seq_len, out=self.static_ids[:, 0])
         return logits
 
     @torch.no_grad()
@@ -124,12 +142,16 @@ class DecodeStepGraph:
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             for _ in range(self.warmup):
-                self.model(self.static_ids, self.caches, start_pos=n)
+                warm = self.model(self.static_ids, self.caches, start_pos=n)
+                if self.sampler is not None:  # (into a scratch buffer: static_ids keeps the caller's tokens)
+                    self.sampler(warm[:, -1], self.pos, out=torch.empty_like(self.static_ids[:, 0]))
                 self._set_len(n)
         torch.cuda.current_stream().wait_stream(side)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.static_logits = self.model(self.static_ids, self.caches, start_pos=n)
+            if self.sampler is not None:  # last in the graph: logits -> static_ids, offset = the advanced length
+                self.sampler(self.static_logits[:, -1], self.pos, out=self.static_ids[:, 0])
         torch.cuda.synchronize()
         self._set_len(n)
 
@@ -144,6 +166,44 @@ class DecodeStepGraph:
         for c in self.caches:  # host bookkeeping of the device-side append
             c.seq_len += 1
         return self.static_logits
+
+    def _check_sampled(self, n: int) -> None:
+        if self.graph is None:
+            raise RuntimeError("DecodeStepGraph: sampled step before prefill")
+        if self.sampler is None:
+            raise RuntimeError("DecodeStepGraph: sampled step without a sampler")
+        if self.seq_len + n > self.caches[0].k.shape[1]:
+            raise RuntimeError("KV cache full")
+
+    @torch.no_grad()
+    def step_sampled(self) -> torch.Tensor:
+        """One replay: consumes the ids in ``static_ids`` and leaves the next ones there (returned: the static
+        buffer [B, 1], overwritten by the next replay).  No host value goes in."""
+        self._check_sampled(1)
+        self.graph.replay()
+        for c in self.caches:
+            c.seq_len += 1
+        return self.static_ids
+
+    @torch.no_grad()
+    def generate(self, n: int, return_logits: bool = False):
+        """``n`` tokens after the ones in ``static_ids``: ids [B, n] from n replays and device-to-device copies,
+        no synchronisation in the loop.  ``return_logits`` also returns each step's logits [B, n, vocab]."""
+        self._check_sampled(n)
+        B = self.static_ids.shape[0]
+        ids = torch.empty(B, n, dtype=torch.long, device=self.static_ids.device)
+        logits = None
+        if return_logits:
+            logits = torch.empty(B, n, self.static_logits.shape[-1], dtype=self.static_logits.dtype,
+                                 device=self.static_ids.device)
+        for i in range(n):
+            self.graph.replay()
+            ids[:, i].copy_(self.static_ids[:, 0])
+            if return_logits:
+                logits[:, i].copy_(self.static_logits[:, -1])
+        for c in self.caches:
+            c.seq_len += n
+        return (ids, logits) if return_logits else ids
 
 
 def explain_cuda_graphs() -> str:

@@ -16,7 +16,7 @@ import torch
 __all__ = [
     "PliError", "lib", "library_path", "available", "DTYPE_CODE",
     "flash_attn_fwd", "gemv", "gemm", "gemm_f32out", "scale_copy", "mfma_probe", "hbm_read_probe", "softmax_rows",
-    "online_softmax_with_output",
+    "online_softmax_with_output", "sample",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -119,6 +119,11 @@ _SIGS = {
     # pli_rms_gemm_nt with (w8, w_scale, wu8, wu_scale) pointer arrays in place of (w, w_up)
     "pli_rms_gemm_nt_fp8w": [_vp, _c_i64, _vp, _c_i64, _vp, _c_f32, _vp, _c_i64, _c_int, _c_int, _c_int,
                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _vp],
+    # next-token sampling: logits, ld, rows, vocab, dtype, temperature, top_k, top_p, uniforms, seed, offset_dev,
+    # offset_add, tokens, ld_tokens, workspace, workspace_bytes, stream
+    "pli_sample_workspace_size": [_c_int] * 3,
+    "pli_sample": [_vp, _c_i64, _c_int, _c_int, _c_int, _c_f32, _c_int, _c_f32, _vp, ctypes.c_uint64, _vp, _c_i64,
+                   _vp, _c_i64, _vp, ctypes.c_size_t, _vp],
     # tuning entry points (include/pli.h tuning section): explicit kernel variant
     "pli_flash_attn_fwd_variant": [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int,
                                    _c_int, ctypes.POINTER(_c_i64), _c_f32, _c_int, _c_int, _vp,
@@ -885,6 +890,50 @@ def moe_combine(y: torch.Tensor, pos: torch.Tensor, weights: torch.Tensor, token
         rc = lib().pli_moe_combine(_ptr(y), y.stride(0), _ptr(pos), _ptr(weights), _ptr(out),
                                    out.stride(0), tokens, k, H, _dtype_code(y), _stream(dev))
     _check(rc, "pli_moe_combine")
+    return out
+
+
+# ----------------------------------------------------------------- sampling
+def sample(logits: torch.Tensor, temperature: float = 1.0, top_k: int | None = None, top_p: float = 1.0, *,
+           uniforms: torch.Tensor | None = None, seed: int = 0, offset=0,
+           out: torch.Tensor | None = None) -> torch.Tensor:
+    """Next token of every row of ``logits`` [..., vocab] (pli_sample, include/pli.h: temperature, top-k, top-p and
+    the draw in one launch): int64 of shape ``logits.shape[:-1]``, -1 for a row with no logit above -inf.
+    ``temperature`` 0 is greedy; ``top_k`` None / <= 0 / >= vocab keeps every token; ``top_p`` >= 1 keeps all of
+    top-k's.  The uniform of row r is ``uniforms[r]`` (device fp32, in [0, 1)) when given, else Philox4x32-10 of
+    (``seed``, offset, r); ``offset`` is an int, an int32 device tensor the KERNEL reads (so a captured call
+    replays while it changes), or a ``(tensor, add)`` pair.  ``out`` may be a strided view (e.g. a column of an
+    id buffer).  A non-unit inner stride of ``logits`` is copied first, as moe_route does."""
+    dev = _require_gpu(logits)
+    if logits.dim() < 1 or logits.shape[-1] < 1:
+        raise PliError(f"sample: logits need a last dimension of at least 1, got shape {tuple(logits.shape)}")
+    lead, V = tuple(logits.shape[:-1]), logits.shape[-1]
+    x = logits.reshape(-1, V)
+    rows = x.shape[0]
+    if x.stride(1) != 1 or (rows > 1 and x.stride(0) < V):
+        x = x.contiguous()
+    if out is None:
+        out = torch.empty(lead, device=logits.device, dtype=torch.int64)
+    elif out.dtype != torch.int64 or out.device != logits.device or tuple(out.shape) != lead:
+        raise PliError(f"sample: out must be int64 {lead} on {logits.device}, got {out.dtype} {tuple(out.shape)} "
+                       f"on {out.device}")
+    try:
+        flat = out if out.dim() == 1 else out.view(-1)
+    except RuntimeError:
+        raise PliError(f"sample: out (strides {out.stride()}) does not flatten to one row stride") from None
+    ld_tokens = flat.stride(0) if rows > 1 else 1
+    off_dev, off_add = (None, offset) if isinstance(offset, int) else offset if isinstance(offset, tuple) else (offset, 0)
+    if off_dev is not None and (off_dev.dtype != torch.int32 or off_dev.device != logits.device or off_dev.numel() < 1):
+        raise PliError("sample: the offset tensor must be int32 on the logits' device")
+    if uniforms is not None:
+        if uniforms.dtype != torch.float32 or uniforms.device != logits.device or uniforms.numel() != rows:
+            raise PliError(f"sample: uniforms must be float32 [{rows}] on the logits' device")
+        uniforms = uniforms.contiguous()
+    with _on_device(dev):
+        rc = lib().pli_sample(_ptr(x), x.stride(0) if rows > 1 else V, rows, V, _dtype_code(x), float(temperature),
+                              int(top_k or 0), float(top_p), _ptr(uniforms), int(seed) & (2 ** 64 - 1),
+                              _ptr(off_dev), int(off_add), _ptr(flat), ld_tokens, None, 0, _stream(dev))
+    _check(rc, "pli_sample")
     return out
 
 
