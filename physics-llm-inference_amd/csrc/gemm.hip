@@ -1843,7 +1843,7 @@ int launch_splitk_swiglu(const void* x, const void* wg, const void* wu, void* h,
 template <typename T>
 int launch_mfma(const void* a, const void* b, void* c, const void* bias, int M, int N, int K,
                 int64_t lda, int64_t ldb, int64_t ldc, int trans_b, hipStream_t s) {
-    const int tm = cdiv(M, BM), tn = cdiv(N, BN);
+    const int tm = cdiv_dim(M, BM), tn = cdiv_dim(N, BN);
     const int64_t nb = (int64_t)tm * tn;
     PLI_REQUIRE(nb < (1ll << 31), "pli_gemm: grid too large");
     const dim3 grid((unsigned)nb), block(256);
@@ -1883,7 +1883,7 @@ int launch_256(const void* a, const void* b, void* c, const void* bias, int M, i
                int64_t lda, int64_t ldb, int64_t ldc, int trans_b, hipStream_t s, int phased,
                bool prio = false, int group_m = 0) {
     // phased: -1 = gemm_256 (one phase per K-tile), else gemm_256p's SCHED bits
-    const int tm = cdiv(M, G2M), tn = cdiv(N, G2N);
+    const int tm = cdiv_dim(M, G2M), tn = cdiv_dim(N, G2N);
     const int64_t nb = (int64_t)tm * tn;
     PLI_REQUIRE(nb < (1ll << 31), "pli_gemm: grid too large");
     const dim3 grid((unsigned)nb), block(512);
@@ -2187,7 +2187,7 @@ static int gemm_dispatch(const void* a, const void* b, void* c, const void* bias
     // M <= 32 with few columns (32 x 2048 x 2048: small-M 8.3 vs 11.3 us);
     // M 33-128 with few columns splits (64 x 2048 x 2048: 11.8 vs 16.7 us)
     const bool short_k = k <= 2048 && m <= 128 && n < 16384 && (m <= 32 || n / 128 >= 64);
-    const bool few_tiles = m > 256 && m <= 2048 && (int64_t)cdiv(m, G2M) * cdiv(n, G2N) < 128;
+    const bool few_tiles = m > 256 && m <= 2048 && (int64_t)cdiv_dim(m, G2M) * cdiv_dim(n, G2N) < 128;
     if (vec && trans_b && splitk_variant(variant) && ws != nullptr && !(variant == 0 && short_k) &&
         (variant != 0 || m <= 256 || few_tiles)) {
         const int target = (variant == 0 && m > 256 && k < 4096) ? 128 : splitk_target(variant);
@@ -2231,7 +2231,7 @@ static int gemm_dispatch(const void* a, const void* b, void* c, const void* bias
     if (variant == 43 && vec && m % 256 == 0 && n % 256 == 0 && gemm_w5_ok(m, n, k, lda, ldb, ldc, trans_b))
         return launch_gemm_w5(a, b, c, bias, m, n, k, lda, ldb, ldc, trans_b, dtype == PLI_BF16, s, 4, true);
     const bool big = vec && k % G2K == 0 && m >= 2 * G2M && n >= 2 * G2N && variant != 1 &&
-                     (variant != 0 || (int64_t)cdiv(m, G2M) * cdiv(n, G2N) >= 128);
+                     (variant != 0 || (int64_t)cdiv_dim(m, G2M) * cdiv_dim(n, G2N) >= 128);
     // default for the large shapes since round 3: gemm_w5 (one wave per SIMD,
     // K staged 64 deep), +10-25 % over the round-2 phased 8-wave tile (variant
     // 13) and at or past hipBLASLt on most shapes (same process, NT / NN TF/s:
@@ -2346,7 +2346,7 @@ extern "C" int pli_gemm_f32out(const void* a, const void* b, float* c, int m, in
     // large shapes (128+ tiles of 256^2): gemm_w5 with its fp32 epilogue
     // (persistent where M, N are multiples of 256 and K >= 128); the
     // TP-8 shard at M 8192 ran 214 us on the split-K kernel below
-    if (lds && m >= 512 && n >= 512 && (int64_t)cdiv(m, 256) * cdiv(n, 256) >= 128 &&
+    if (lds && m >= 512 && n >= 512 && (int64_t)cdiv_dim(m, 256) * cdiv_dim(n, 256) >= 128 &&
         gemm_w5_ok(m, n, k, lda, ldb, n, 1)) {
         const bool persist = m % 256 == 0 && n % 256 == 0 && k >= 128;
         return launch_gemm_w5(a, b, c, nullptr, m, n, k, lda, ldb, n, 1, dtype == PLI_BF16, s, 4, persist, true);

@@ -346,7 +346,7 @@ int launch_gemm_w4v(const void* a, const void* b, void* c, const void* bias, int
                     int64_t ldb, int64_t ldc, int trans_b, int is_bf16, hipStream_t stream, int group_m) {
     PLI_REQUIRE(gemm_w4v_ok(m, n, k, lda, ldb, ldc, trans_b), "gemm_w4v: shape m=%d n=%d k=%d not supported", m,
                 n, k);
-    const int tiles_m = cdiv(m, 256), tiles_n = cdiv(n, 256);
+    const int tiles_m = cdiv_dim(m, 256), tiles_n = cdiv_dim(n, 256);
     const int64_t nb = (int64_t)tiles_m * tiles_n;
     PLI_REQUIRE(nb < (1ll << 31), "gemm_w4v: grid too large");
     const auto* A = (const uint16_t*)a;

@@ -760,7 +760,7 @@ int launch_gemm_w5(const void* a, const void* b, void* c, const void* bias, int 
     group_m = W5_GROUP_M;  // A/B builds only
 #endif
     PLI_REQUIRE(group_m >= 1, "gemm_w5: group_m must be >= 1");
-    const int tiles_m = cdiv(m, 256), tiles_n = cdiv(n, 256);
+    const int tiles_m = cdiv_dim(m, 256), tiles_n = cdiv_dim(n, 256);
     const int64_t nb = (int64_t)tiles_m * tiles_n;
     PLI_REQUIRE(nb < (1ll << 31), "gemm_w5: grid too large");
     const auto* A = (const uint16_t*)a;

@@ -27,6 +27,11 @@ __device__ __forceinline__ void dot_chunk<bf16_t>(const i32x4& w, const i32x4& x
 }
 template <>
 __device__ __forceinline__ void dot_chunk<f16_t>(const i32x4& w, const i32x4& x, float& acc) {
+    // two FMAs per pair, each rounded, as gemm_skinny_nt's.  Left to itself
+    // hipcc folds the pair into v_dot2c_f32_f16, which rounds once, and
+    // y = W x through pli_gemm (M = 1) is then an ulp off the skinny kernel
+    // now and then (tests/test_gpu_gemm.py, K = 1024); the empty asm keeps the
+    // two apart and emits nothing
     typedef __attribute__((ext_vector_type(2))) _Float16 h2;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -35,6 +40,7 @@ __device__ __forceinline__ void dot_chunk<f16_t>(const i32x4& w, const i32x4& x,
         const int wi = w[i], xi = x[i];
         const h2 a = __builtin_bit_cast(h2, wi), b = __builtin_bit_cast(h2, xi);
         acc = fmaf((float)a.x, (float)b.x, acc);
+        asm volatile("" : "+v"(acc));
         acc = fmaf((float)a.y, (float)b.y, acc);
     }
 }

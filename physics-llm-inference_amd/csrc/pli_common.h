@@ -166,6 +166,9 @@ __device__ __forceinline__ float wave_sum(float x) {
 }
 
 __host__ __device__ constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
+// cdiv for a host-side dimension a >= 0 of any size: a + b - 1 overflows within
+// b of 2^31, and the negative tile count then slips past a "grid too large" rule
+constexpr int cdiv_dim(int a, int b) { return a / b + (a % b != 0); }
 
 // XCD-aware remap (bijective for any grid): blocks b and b+8 share an XCD
 // under the observed round-robin dispatch, so give each XCD a contiguous
