@@ -748,6 +748,60 @@ int pli_rms_gemm_nt_fp8w(const void* a, int64_t lda, const void* residual, int64
                          const int32_t* const* row_offset, const int* capacity,
                          int ngroups, int dtype, void* stream);
 
+/* fp8 activations (W8A8): a row quantiser and an NT GEMM over two operands of
+ * e4m3fn codes on the block-scaled matrix instruction of gfx950
+ * (v_mfma_scale_f32_32x32x64_f8f6f4, e4m3 x e4m3 at twice the bf16 MFMA rate
+ * per clock), for prefill and batches above the decode kernels' 16 rows.
+ *
+ * pli_quantize_rows_fp8: x [m, k] bf16 / fp16 (ldx in elements; PLI_F32 is
+ *   refused) -> x8 [m, k] e4m3fn codes (ldx8 in bytes) and x_scale, device
+ *   fp32 [m], both written by the call.  Per row, the rule of the Python
+ *   quantize_weight_fp8: scale = absmax / 448 in fp32 (1.0 for a row with no
+ *   non-zero finite element), inv = 1.0f / scale, code = e4m3fn(clamp(fp32(x)
+ *   * inv, +-448)), round to nearest even; for finite rows codes and scales
+ *   are bitwise that function's.  A device call cannot raise, so: a NaN
+ *   element is skipped by the absmax and gets code 0x7F; +-inf is skipped by
+ *   the absmax and gets the code of +-448 (0x7E / 0xFE).
+ *   Kernel "quant_rows_fp8", one workgroup per row.  With k and ldx multiples
+ *   of 8, ldx8 a multiple of 8, x 16-byte and x8 8-byte aligned a row of up to
+ *   8192 elements is read once (held in registers between the absmax and the
+ *   encode) and the rest of a longer one twice; any other call reads x twice.
+ *   k == 0 writes scale 1.0 and no codes; m == 0 does nothing.
+ * pli_gemm_fp8: C[r, j] = round_T( x_scale[r] * w_scale[j] *
+ *   sum_i decode(x8[r, i]) * decode(w8[j, i])  (+ bias[j]) ).  x8 [m, k] and
+ *   w8 [n, k] codes, leading dimensions ldx8 / ldw in bytes; T (dtype) is
+ *   bf16 or fp16 and is the type of C (ldc in elements) and bias.  Either
+ *   scale pointer may be NULL: all ones.  Both scales are device fp32, read
+ *   on the device: a captured call replays while codes and scales change in
+ *   place.  A code x code product has at most 8 significant bits and is exact
+ *   in fp32; the sum is fp32; sum * (x_scale[r] * w_scale[j]) and the bias
+ *   come after the sum and the result is rounded once.  A NaN code in x8
+ *   makes exactly its row of C NaN, one in w8 exactly its column.  No
+ *   workspace; nothing is allocated or synchronised.
+ * Routes, in this order, from host arguments only (csrc/fp8a_plan.h;
+ *   pli_last_route names the kernel):
+ *   1. k == 0: C = bias or 0 ("gemm_fp8_generic"); m == 0 or n == 0: nothing.
+ *   2. "gemm_fp8_mx": m >= 17, k % 128 == 0, x8 / w8 16-byte aligned, ldx8
+ *      and ldw % 16 == 0, n and ldc % 4 == 0, c 8-byte aligned.  128 x 128
+ *      tile, codes staged by 16-byte LDS-DMA into a swizzled two-stage LDS
+ *      image, K-step 128, both E8M0 block scales at 2^0; ragged m / n edges
+ *      by clamped loads and masked stores.  The order in which the
+ *      instruction sums its 64 products is its own, so this route agrees with
+ *      route 3 to fp32 rounding, and bitwise only where every partial sum is
+ *      exact.
+ *   3. "gemm_fp8_generic": one thread per output, fp32 fma in k order, any
+ *      shape, leading dimension and alignment.
+ * PLI_EINVAL before any HIP call, in this order: a dtype other than fp16 /
+ *   bf16, a negative shape, a leading dimension below its width, a NULL
+ *   operand of a non-empty call (x_scale of the quantiser included; the
+ *   GEMM's scales and bias may be NULL), a grid too large. */
+int pli_quantize_rows_fp8(const void* x, int64_t ldx, void* x8, int64_t ldx8,
+                          float* x_scale, int m, int k, int dtype, void* stream);
+int pli_gemm_fp8(const void* x8, const float* x_scale, const void* w8,
+                 const float* w_scale, const void* bias, void* c, int m, int n,
+                 int k, int64_t ldx8, int64_t ldw, int64_t ldc, int dtype,
+                 void* stream);
+
 /* Next-token sampling on the device: temperature, top-k, top-p and the draw of
  * ch02/generation.py:23-31 (temperature, top-k, multinomial),
  * ch02/cached_generation.py:245,265 (temperature) and ch10/engine.py:96-115

@@ -119,6 +119,9 @@ _SIGS = {
     # pli_rms_gemm_nt with (w8, w_scale, wu8, wu_scale) pointer arrays in place of (w, w_up)
     "pli_rms_gemm_nt_fp8w": [_vp, _c_i64, _vp, _c_i64, _vp, _c_f32, _vp, _c_i64, _c_int, _c_int, _c_int,
                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _vp],
+    # fp8 activations (W8A8): the row quantiser and the codes x codes NT GEMM
+    "pli_quantize_rows_fp8": [_vp, _c_i64, _vp, _c_i64, _vp, _c_int, _c_int, _c_int, _vp],
+    "pli_gemm_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_int, _vp],
     # next-token sampling: logits, ld, rows, vocab, dtype, temperature, top_k, top_p, uniforms, seed, offset_dev,
     # offset_add, tokens, ld_tokens, workspace, workspace_bytes, stream
     "pli_sample_workspace_size": [_c_int] * 3,
@@ -1282,6 +1285,124 @@ def linear_swiglu_fp8w(x: torch.Tensor, g_codes: torch.Tensor, g_scale: torch.Te
                                           _stream(dev))
     _check(rc, "pli_linear_swiglu_fp8w")
     return out
+
+
+# ------------------------------------------------- fp8 activations (W8A8)
+FP8A_MIN_ROWS = 17  # csrc/fp8a_plan.h kFp8aMinM: fewer rows stay on the W8A16 decode kernels
+
+
+def _quantize_rows_fp8_torch(x: torch.Tensor):
+    """the rule of pli_quantize_rows_fp8 in torch ops (any device): quantize_weight_fp8 per row, with the
+    non-finite rule a device call needs (NaN -> 0x7F, +-inf -> +-448, neither enters the absmax)"""
+    xf = x.detach().float()
+    m = xf.shape[0]
+    finite = torch.isfinite(xf)
+    amax = (torch.where(finite, xf.abs(), torch.zeros_like(xf)).amax(dim=1) if xf.shape[1]
+            else torch.zeros(m, dtype=torch.float32, device=xf.device))
+    scale = torch.where(amax > 0, amax / FP8_E4M3_MAX, torch.ones_like(amax)).contiguous()
+    inv = 1.0 / scale
+    nan = torch.isnan(xf)
+    y = torch.where(nan, torch.zeros_like(xf), xf) * inv[:, None]
+    codes = y.clamp(-FP8_E4M3_MAX, FP8_E4M3_MAX).to(torch.float8_e4m3fn)
+    if bool(nan.any()):
+        codes.view(torch.uint8)[nan] = 0x7F
+    return codes, scale
+
+
+def quantize_rows_fp8(x: torch.Tensor, out: tuple | None = None):
+    """Per-row e4m3fn quantisation of activations x [m, k] fp16 / bf16: ``(codes, scale)`` with codes
+    ``torch.float8_e4m3fn`` [m, k] and scale fp32 [m], value = code * scale[row].  The rule is quantize_weight_fp8's
+    per row (bitwise for finite rows); a NaN element gets code 0x7F, +-inf the code of +-448, and neither enters the
+    absmax.  On a device tensor this is the quant_rows_fp8 kernel, on a CPU tensor torch ops.  ``out``: a
+    (codes, scale) pair to write into (device path; codes float8_e4m3fn / uint8 with a unit column stride)."""
+    if x.dim() != 2:
+        raise PliError(f"quantize_rows_fp8 expects a 2-D x, got {tuple(x.shape)}")
+    if x.dtype not in (torch.float16, torch.bfloat16):
+        raise PliError(f"quantize_rows_fp8: activations must be fp16 or bf16, got {x.dtype}")
+    if not x.is_cuda:
+        if out is not None:
+            raise PliError("quantize_rows_fp8: out is for the device path")
+        return _quantize_rows_fp8_torch(x)
+    dev = x.device
+    if x.numel() and x.stride(1) != 1:
+        x = x.contiguous()
+    m, k = x.shape
+    if out is None:
+        codes = torch.empty((m, k), dtype=torch.float8_e4m3fn, device=dev)
+        scale = torch.empty((m,), dtype=torch.float32, device=dev)
+    else:
+        codes, scale = out
+        if (not codes.is_cuda or codes.device != dev or codes.dtype not in FP8_POOL_DTYPES or
+                tuple(codes.shape) != (m, k) or (codes.numel() and codes.stride(1) != 1)):
+            raise PliError(f"quantize_rows_fp8: out codes must be float8_e4m3fn / uint8 [{m}, {k}] on {dev} with a "
+                           "unit column stride")
+        if (not scale.is_cuda or scale.device != dev or scale.dtype != torch.float32 or tuple(scale.shape) != (m,) or
+                not scale.is_contiguous()):
+            raise PliError(f"quantize_rows_fp8: out scale must be a contiguous fp32 [{m}] tensor on {dev}")
+    with _on_device(dev):
+        rc = lib().pli_quantize_rows_fp8(_ptr(x), max(x.stride(0), k) if m > 1 else k, _ptr(codes), _ldw(codes),
+                                         _ptr(scale), m, k, _dtype_code(x), _stream(dev))
+    _check(rc, "pli_quantize_rows_fp8")
+    return codes, scale
+
+
+def _check_fp8a(what: str, x8: torch.Tensor, x_scale, w8: torch.Tensor, w_scale) -> torch.device:
+    if not x8.is_cuda or not w8.is_cuda:
+        raise PliError("HIP path called with a CPU tensor")
+    dev = x8.device
+    if x8.dim() != 2 or w8.dim() != 2 or x8.shape[1] != w8.shape[1]:
+        raise PliError(f"{what} shape mismatch: x8{tuple(x8.shape)} w8{tuple(w8.shape)}")
+    for name, codes, scale in (("x", x8, x_scale), ("w", w8, w_scale)):
+        if codes.device != dev or codes.dtype not in FP8_POOL_DTYPES:
+            raise PliError(f"{what}: {name}8 must be a torch.float8_e4m3fn or torch.uint8 tensor on {dev}, "
+                           f"got {codes.dtype} on {codes.device}")
+        if codes.numel() and codes.stride(1) != 1:
+            raise PliError(f"{what}: {name}8 needs a unit column stride (the codes are used in place)")
+        rows = codes.shape[0]
+        if scale is not None and (not scale.is_cuda or scale.device != dev or scale.dtype != torch.float32 or
+                                  tuple(scale.shape) != (rows,) or not scale.is_contiguous()):
+            raise PliError(f"{what}: {name}_scale must be None or a contiguous fp32 [{rows}] tensor on {dev}")
+    return dev
+
+
+def gemm_fp8(x8: torch.Tensor, x_scale: torch.Tensor | None, w8: torch.Tensor, w_scale: torch.Tensor | None,
+             bias: torch.Tensor | None = None, out_dtype: torch.dtype = torch.bfloat16,
+             out: torch.Tensor | None = None) -> torch.Tensor:
+    """C = (x_scale[:, None] * decode(x8)) (w_scale[:, None] * decode(w8))^T (+ bias) over two operands of e4m3fn
+    codes: x8 [m, k], w8 [n, k] (float8_e4m3fn or uint8, any row stride, used in place), scales fp32 [m] / [n] or None
+    (ones), C and bias ``out_dtype`` (bf16 / fp16).  fp32 sum, scales and bias after the sum, one rounding."""
+    dev = _check_fp8a("gemm_fp8", x8, x_scale, w8, w_scale)
+    if out_dtype not in (torch.float16, torch.bfloat16):
+        raise PliError(f"gemm_fp8: out_dtype must be fp16 or bf16, got {out_dtype}")
+    m, k = x8.shape
+    n = w8.shape[0]
+    if bias is not None:
+        if not bias.is_cuda or bias.device != dev or bias.dtype != out_dtype or tuple(bias.shape) != (n,):
+            raise PliError(f"gemm_fp8: bias must be a {out_dtype} [{n}] tensor on {dev}")
+        bias = bias.contiguous()
+    if out is None:
+        out = torch.empty((m, n), dtype=out_dtype, device=dev)
+    else:
+        if out.dtype != out_dtype:
+            raise PliError(f"gemm_fp8: out is {out.dtype}, out_dtype {out_dtype}")
+        _check_out(out, out, (m, n), "gemm_fp8")
+        if out.device != dev:
+            raise PliError(f"tensors on different devices: {out.device} vs {dev}")
+    with _on_device(dev):
+        rc = lib().pli_gemm_fp8(_ptr(x8), _ptr(x_scale), _ptr(w8), _ptr(w_scale), _ptr(bias), _ptr(out), m, n, k,
+                                _ldw(x8), _ldw(w8), max(out.stride(0), n), DTYPE_CODE[out_dtype], _stream(dev))
+    _check(rc, "pli_gemm_fp8")
+    return out
+
+
+def linear_fp8a(x: torch.Tensor, w8: torch.Tensor, w_scale: torch.Tensor | None, bias: torch.Tensor | None = None,
+                out: torch.Tensor | None = None) -> torch.Tensor:
+    """x W^T (+ bias) with both operands in fp8: quantize_rows_fp8(x), then gemm_fp8 against the weight codes
+    (W = decode(w8) * w_scale[:, None], as linear_fp8w takes them); the result has x's dtype.  Bitwise the two calls."""
+    if not x.is_cuda:
+        raise PliError("HIP path called with a CPU tensor")
+    x8, x_scale = quantize_rows_fp8(x)
+    return gemm_fp8(x8, x_scale, w8, w_scale, bias=bias, out_dtype=x.dtype, out=out)
 
 
 def _rms_gemm_fp8w(a: torch.Tensor, norm_weight: torch.Tensor, eps: float, groups: list,
