@@ -700,6 +700,83 @@ int pli_linear_swiglu_fp8w(const void* x, const void* wg8,
                            int64_t ldx, int64_t ldwg, int64_t ldwu,
                            int64_t ldh, int dtype, void* workspace,
                            size_t workspace_bytes, void* stream);
+/* Weight-only MXFP4 linear (W4A16) for decode batches: the weight stream of
+ * the fp8 calls above at 4.25 bits per element (OCP Microscaling FP4).
+ *
+ * Codes: w4 [n, k / 2] bytes, row-major, leading dimension ldw in bytes
+ *   (>= k / 2).  Element i of a row lives in byte i / 2: even i in bits 3:0,
+ *   odd i in bits 7:4.  A code is e2m1: sign(1) | exponent(2) | mantissa(1),
+ *   magnitudes {0, 0.5, 1, 1.5, 2, 3, 4, 6}; no NaN, no infinity, -0 is 0.
+ * Scales: w_exp [n, k / 32] bytes (leading dimension lds >= k / 32), E8M0:
+ *   byte s is 2^(s - 127), 0xFF is NaN.  Block b of row j covers k in
+ *   [32 b, 32 b + 32).  Both arrays are device memory read on the device (a
+ *   captured call replays while they change in place).  w_exp has no
+ *   default and may not be NULL.
+ * Shape: k % 32 == 0 on every route (a block never straddles a row end).
+ * Value: element (j, i) = decode(code) * 2^(w_exp[j, i / 32] - 127).
+ * Result: C[r, j] = round_T( sum_i value(j, i) * X[r, i] (+ bias[j]) ), the
+ *   sum in fp32 and one rounding to T.  T (dtype) is bf16 or fp16 and is the
+ *   type of X, C and bias; PLI_F32 is refused.
+ * SwiGLU: h = silu(sum g) * (sum u), silu(g) = g / (1 + e^-g) as
+ *   pli_gemm_swiglu; neither gate nor up is written.
+ * Scale contract: every scale byte of a call has s - 127 in [-125, 125] for
+ *   bf16 and in [-13, 13] for fp16.  Then every element value is a normal
+ *   number of T, the kernels widen codes to T with the block scale folded in
+ *   and no rounding, a value x 16-bit product is exact in fp32, and the
+ *   result is the 16-bit linear over the dequantised weights.  Outside the
+ *   contract the outputs of that weight row are unspecified, but no access
+ *   leaves an operand.  A 0xFF scale byte makes exactly the outputs of its
+ *   row j NaN, in all m rows, on every route.
+ * Routes, in this order, from host arguments only (csrc/mxfp4w_plan.h;
+ *   pli_last_route names the kernels):
+ *   1. k == 0: C = bias or 0 ("mxfp4w_generic"); m == 0 or n == 0: nothing.
+ *   2. "mxfp4w_smallm" (MFMA 16x16x32, the scale folded into the A operand):
+ *      1 < m <= 128, k % 512 == 0, n % 16 == 0, w4 / x / c 16-byte aligned,
+ *      ldw % 16 == 0, ldx and ldc % 8 == 0.
+ *   3. "mxfp4w_vec" (VALU, one wave per 2 / 4 / 8 weight rows): m <= 16,
+ *      ldw % 16 == 0, ldx % 8 == 0, w4 / x 16-byte aligned.  Its MACs are
+ *      v_dot2 on the packed pairs (fp32 accumulate), so it agrees with the
+ *      other routes to fp32 rounding, not bitwise.
+ *   4. "mxfp4w_widen+<pli_gemm's route>": m > 16, no fast route, a workspace
+ *      given, and pli_gemm's vector class (n, ldx, ldc % 8 == 0, x / c
+ *      16-byte aligned, bias 8-byte aligned).  The codes are widened to
+ *      T(value) into the workspace, contiguous [n][k], and the existing
+ *      pli_gemm (trans_b = 1) or pli_gemm_swiglu (gate, then up at the next
+ *      16-byte boundary) runs over them: the prefill path.
+ *   5. "mxfp4w_generic": one thread per output, any m, n, leading dimension
+ *      and alignment.
+ *   The scale bytes are read one at a time: neither w_exp's address nor lds
+ *   enters the rule.  The SwiGLU kernels report "<name><swiglu>".
+ * Workspace: pli_linear_mxfp4w_workspace_size is 0 for m <= 16 and for
+ *   m <= 128 with k % 512 == 0 and n % 16 == 0 (a fast route takes aligned
+ *   operands), else n * k * 2 rounded up to 16 bytes; twice that for SwiGLU.
+ *   Caller-owned, 16-byte aligned scratch; nothing persists between calls.
+ *   Without one (NULL) such a shape takes the generic kernel.
+ * pli_gemv_mxfp4w: y[m] = w4[m, k] x, pli_linear_mxfp4w with one X row and no
+ *   bias on the same kernel, bitwise equal to it.
+ * PLI_EINVAL before any HIP call: a dtype other than fp16 / bf16, a negative
+ *   shape, k % 32 != 0, a leading dimension below its width, a NULL operand
+ *   of a non-empty call (w_exp included), a misaligned or short workspace
+ *   when route 4 would be taken.  m == 0 or n == 0 returns PLI_OK and the
+ *   operands may be NULL; k == 0 writes bias or 0 and reads neither x nor the
+ *   weights.  Nothing is allocated or synchronised. */
+int pli_gemv_mxfp4w(const void* w4, const void* w_exp, const void* x, void* y,
+                    int m, int k, int64_t ldw, int64_t lds, int dtype,
+                    void* stream);
+size_t pli_linear_mxfp4w_workspace_size(int m, int n, int k, int dtype);
+int pli_linear_mxfp4w(const void* x, const void* w4, const void* w_exp,
+                      const void* bias, void* c, int m, int n, int k,
+                      int64_t ldx, int64_t ldw, int64_t lds, int64_t ldc,
+                      int dtype, void* workspace, size_t workspace_bytes,
+                      void* stream);
+size_t pli_linear_swiglu_mxfp4w_workspace_size(int m, int n, int k, int dtype);
+int pli_linear_swiglu_mxfp4w(const void* x, const void* wg4,
+                             const void* wg_exp, const void* wu4,
+                             const void* wu_exp, void* h, int m, int n, int k,
+                             int64_t ldx, int64_t ldwg, int64_t ldsg,
+                             int64_t ldwu, int64_t ldsu, int64_t ldh,
+                             int dtype, void* workspace,
+                             size_t workspace_bytes, void* stream);
 /* pli_rms_gemm_nt_fp8w: pli_rms_gemm_nt over fp8 weights -- a decode-step
  * RMSNorm fused into the W8A16 projection that consumes it, one launch
  * (kernel "rms_gemm_fp8w": the norm phase of pli_rms_gemm_nt in front of the

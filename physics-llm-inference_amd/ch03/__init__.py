@@ -6,7 +6,8 @@ from .batching_benchmark import (
     find_transition_batch_size,
 )
 from .gemm_benchmark import benchmark_gemm, gemm_bytes, gemm_flops
-from .gemv_benchmark import benchmark_gemv, benchmark_gemv_fp8w, gemv_bytes, gemv_flops, gemv_fp8w_bytes
+from .gemv_benchmark import (benchmark_gemv, benchmark_gemv_fp8w, benchmark_gemv_mxfp4w, gemv_bytes, gemv_flops,
+                             gemv_fp8w_bytes, gemv_mxfp4w_bytes)
 from .roofline import (
     MI355X,
     arithmetic_intensity,
@@ -24,6 +25,8 @@ __all__ = [
     "gemv_bytes",
     "benchmark_gemv_fp8w",
     "gemv_fp8w_bytes",
+    "benchmark_gemv_mxfp4w",
+    "gemv_mxfp4w_bytes",
     "arithmetic_intensity",
     "roofline_throughput",
     "is_compute_bound",

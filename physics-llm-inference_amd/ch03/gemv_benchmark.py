@@ -145,6 +145,48 @@ def benchmark_gemv_fp8w(
     return summarize(times, gemv_flops(m, k), gemv_fp8w_bytes(m, k, dtype), kernel_us)
 
 
+def gemv_mxfp4w_bytes(m: int, k: int, dtype: torch.dtype = torch.bfloat16) -> int:
+    """Compulsory bytes with MXFP4 weights (4.25 bits each): codes (m*k/2) + E8M0 scales (m*k/32) + x (2k) + y (2m)."""
+    return m * k // 2 + m * k // 32 + (k + m) * _elem(dtype)
+
+
+def benchmark_gemv_mxfp4w(
+    m: int,
+    k: int,
+    dtype: torch.dtype = torch.bfloat16,
+    warmup: int = 10,
+    iterations: int = 100,
+    device: str = "cuda",
+) -> BenchmarkResult:
+    """benchmark_gemv over MXFP4 weights (e2m1 codes, one E8M0 scale per 32; ``pli_gemv_mxfp4w``,
+    csrc/linear_mxfp4w.hip): the same method and fields, the 4.25-bit byte count.  On the CPU
+    the dequantised torch.mv is timed instead."""
+    codes, exps = pli_hip.quantize_weight_mxfp4(torch.randn(m, k, dtype=torch.float32, device=device), dtype)
+    x = torch.randn(k, dtype=dtype, device=device)
+    on_gpu = codes.is_cuda
+    y = torch.empty(m, dtype=dtype, device=device)
+    weight = None if on_gpu else pli_hip.dequantize_weight_mxfp4(codes, exps).to(dtype)
+
+    def call():
+        if on_gpu:
+            pli_hip.gemv_mxfp4w(codes, exps, x, out=y)
+        else:
+            torch.mv(weight, x)
+
+    for _ in range(warmup):
+        call()
+    _sync(device)
+    times = []
+    for _ in range(iterations):
+        _sync(device)
+        t0 = time.perf_counter()
+        call()
+        _sync(device)
+        times.append((time.perf_counter() - t0) * 1e6)
+    kernel_us = _event_time_us(call, iterations) if on_gpu else None
+    return summarize(times, gemv_flops(m, k), gemv_mxfp4w_bytes(m, k, dtype), kernel_us)
+
+
 def benchmark_decode_gemv(hidden_dim: int, dtype: torch.dtype = torch.float16) -> BenchmarkResult:
     return benchmark_gemv(hidden_dim, hidden_dim, dtype=dtype)
 

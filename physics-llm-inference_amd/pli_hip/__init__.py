@@ -116,6 +116,14 @@ _SIGS = {
     "pli_linear_swiglu_fp8w_workspace_size": [_c_int] * 4,
     "pli_linear_swiglu_fp8w": [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_i64,
                                _c_int, _vp, ctypes.c_size_t, _vp],
+    # weight-only MXFP4 linear (W4A16): e2m1 code bytes + one E8M0 scale byte per 32 elements
+    "pli_gemv_mxfp4w": [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_i64, _c_i64, _c_int, _vp],
+    "pli_linear_mxfp4w_workspace_size": [_c_int] * 4,
+    "pli_linear_mxfp4w": [_vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _vp,
+                          ctypes.c_size_t, _vp],
+    "pli_linear_swiglu_mxfp4w_workspace_size": [_c_int] * 4,
+    "pli_linear_swiglu_mxfp4w": [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_i64,
+                                 _c_i64, _c_i64, _c_int, _vp, ctypes.c_size_t, _vp],
     # pli_rms_gemm_nt with (w8, w_scale, wu8, wu_scale) pointer arrays in place of (w, w_up)
     "pli_rms_gemm_nt_fp8w": [_vp, _c_i64, _vp, _c_i64, _vp, _c_f32, _vp, _c_i64, _c_int, _c_int, _c_int,
                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _vp],
@@ -1284,6 +1292,163 @@ def linear_swiglu_fp8w(x: torch.Tensor, g_codes: torch.Tensor, g_scale: torch.Te
                                           _ldw(u_codes), max(out.stride(0), n), _dtype_code(x), wsp, wsb,
                                           _stream(dev))
     _check(rc, "pli_linear_swiglu_fp8w")
+    return out
+
+
+# --------------------------------------- weight-only MXFP4 linear (W4A16)
+MXFP4_BLOCK = 32
+# the scale contract of include/pli.h: s - 127 of every scale byte, per activation dtype
+MXFP4_EXP_RANGE = {torch.bfloat16: (-125, 125), torch.float16: (-13, 13)}
+_E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def quantize_weight_mxfp4(w: torch.Tensor, dtype: torch.dtype = torch.bfloat16):
+    """OCP MXFP4 quantisation of a weight [n, k], k % 32 == 0 (torch ops only; CPU or GPU): ``(codes, exps)`` with
+    codes uint8 [n, k / 2] (element i in byte i / 2, even i in bits 3:0) and exps uint8 [n, k / 32] (E8M0).  Per
+    block of 32 along k: e = floor(log2(amax)) - 2 clamped into ``dtype``'s scale-contract range (e = 0 and all codes
+    0 for an all-zero block), exps = e + 127, each code the e2m1 round-to-nearest-even of clamp(w / 2^e, -6, 6).
+    Non-finite weights raise ``ValueError``."""
+    if w.dim() != 2 or w.shape[1] % MXFP4_BLOCK:
+        raise ValueError(f"quantize_weight_mxfp4 expects a [n, k] weight with k % 32 == 0, got {tuple(w.shape)}")
+    if dtype not in MXFP4_EXP_RANGE:
+        raise ValueError(f"quantize_weight_mxfp4: dtype must be bf16 or fp16, got {dtype}")
+    wf = w.detach().float()
+    if not bool(torch.isfinite(wf).all()):
+        raise ValueError("quantize_weight_mxfp4: non-finite weight")
+    n, k = wf.shape
+    blk = wf.reshape(n, k // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = blk.abs().amax(dim=2)
+    lo, hi = MXFP4_EXP_RANGE[dtype]
+    # amax = f * 2^x with f in [0.5, 1): floor(log2(amax)) = x - 1, exactly
+    e = torch.where(amax > 0, torch.frexp(amax)[1] - 3, torch.zeros_like(amax, dtype=torch.int32)).clamp(lo, hi)
+    y = torch.ldexp(blk, -e[:, :, None]).clamp(-6.0, 6.0)  # exact scaling by a power of two
+    a = y.abs()
+    # round to nearest even on the e2m1 grid: step 0.5 below 2, 1 below 4, 2 up to 6 (torch.round is half-to-even)
+    mag = torch.where(a < 2, torch.round(a * 2), torch.where(a < 4, torch.round(a) + 2, torch.round(a / 2) + 4))
+    code = (mag.to(torch.uint8) | (torch.signbit(y).to(torch.uint8) << 3)).reshape(n, k)
+    codes = (code[:, 0::2] | (code[:, 1::2] << 4)).contiguous()
+    return codes, (e + 127).to(torch.uint8).contiguous()
+
+
+def dequantize_weight_mxfp4(codes: torch.Tensor, exps: torch.Tensor) -> torch.Tensor:
+    """float32 [n, k] of codes uint8 [n, k / 2] and exps uint8 [n, k / 32]: decode(code) * 2^(exps - 127), exact;
+    a 0xFF scale byte makes its block NaN.  The definition the kernels are tested against."""
+    if codes.dim() != 2 or exps.dim() != 2 or codes.shape[0] != exps.shape[0] or codes.shape[1] != exps.shape[1] * 16:
+        raise ValueError(f"dequantize_weight_mxfp4: codes{tuple(codes.shape)} exps{tuple(exps.shape)} do not match")
+    n = codes.shape[0]
+    c = codes.view(torch.uint8) if codes.dtype != torch.uint8 else codes
+    nib = torch.stack((c & 15, c >> 4), dim=2).reshape(n, -1).long()
+    mag = torch.tensor(_E2M1_VALUES, dtype=torch.float32, device=c.device)[nib & 7]
+    val = torch.where(nib >= 8, -mag, mag).reshape(n, -1, MXFP4_BLOCK)
+    out = torch.ldexp(val, (exps.to(torch.int32) - 127)[:, :, None])
+    return torch.where((exps == 0xFF)[:, :, None], torch.full_like(out, float("nan")), out).reshape(n, -1)
+
+
+def _check_mxfp4w(what: str, x: torch.Tensor, weights) -> torch.device:
+    """x [m, k] fp16 / bf16 on a device; each (codes, exps): uint8 [n, k / 2] and [n, k / 32] with unit column
+    strides, on x's device"""
+    dev = _require_gpu(x)
+    if x.dtype not in (torch.float16, torch.bfloat16):
+        raise PliError(f"{what}: activations must be fp16 or bf16, got {x.dtype}")
+    k = x.shape[-1]
+    if k % MXFP4_BLOCK:
+        raise PliError(f"{what}: k = {k} is not a multiple of the MX block of 32")
+    n = None
+    for codes, exps in weights:
+        for t, name, width in ((codes, "codes", k // 2), (exps, "exps", k // MXFP4_BLOCK)):
+            if not isinstance(t, torch.Tensor):
+                raise PliError(f"{what}: {name} must be a tensor, got {type(t).__name__} (the scale bytes have no default)")
+            if n is None:
+                n = t.shape[0] if t.dim() == 2 else -1
+            if not t.is_cuda:
+                raise PliError("HIP path called with a CPU tensor")
+            if t.device != dev or t.dtype != torch.uint8:
+                raise PliError(f"{what}: {name} must be a torch.uint8 tensor on {dev}, got {t.dtype} on {t.device}")
+            if t.dim() != 2 or t.shape[0] != n or t.shape[1] != width:
+                raise PliError(f"{what} shape mismatch: x{tuple(x.shape)} {name}{tuple(t.shape)}")
+            if t.numel() and t.stride(1) != 1:
+                raise PliError(f"{what}: {name} need a unit column stride (they are used in place)")
+    return dev
+
+
+def linear_mxfp4w_workspace_bytes(m: int, n: int, k: int, dtype: torch.dtype = torch.bfloat16,
+                                  swiglu: bool = False) -> int:
+    """bytes of workspace linear_mxfp4w (linear_swiglu_mxfp4w with ``swiglu``) wants for [m, k] x [n, k]^T; 0: none"""
+    fn = lib().pli_linear_swiglu_mxfp4w_workspace_size if swiglu else lib().pli_linear_mxfp4w_workspace_size
+    return int(fn(int(m), int(n), int(k), DTYPE_CODE.get(dtype, -1)))
+
+
+def linear_mxfp4w(x: torch.Tensor, codes: torch.Tensor, exps: torch.Tensor, bias: torch.Tensor | None = None,
+                  out: torch.Tensor | None = None, workspace: torch.Tensor | None = None) -> torch.Tensor:
+    """C = x W^T (+ bias) over MXFP4 weights: x [m, k] fp16 / bf16, codes uint8 [n, k / 2] and exps uint8 [n, k / 32]
+    used in place (any row stride); W = dequantize_weight_mxfp4(codes, exps).  ``workspace`` (bytes from
+    linear_mxfp4w_workspace_bytes) lets m > 16 shapes without a fast kernel run widen + the 16-bit GEMM."""
+    if x.dim() != 2:
+        raise PliError(f"linear_mxfp4w expects a 2-D x, got {tuple(x.shape)}")
+    dev = _check_mxfp4w("linear_mxfp4w", x, [(codes, exps)])
+    if x.stride(1) != 1:
+        x = x.contiguous()
+    m, k = x.shape
+    n = codes.shape[0]
+    if bias is not None:
+        _require_gpu(x, bias)
+        bias = bias.contiguous()
+        if tuple(bias.shape) != (n,):
+            raise PliError(f"bias must be [{n}]")
+    if out is None:
+        out = torch.empty((m, n), dtype=x.dtype, device=dev)
+    else:
+        _check_out(out, x, (m, n), "linear_mxfp4w")
+    wsp, wsb = _fp8w_workspace("linear_mxfp4w", workspace, dev)
+    with _on_device(dev):
+        rc = lib().pli_linear_mxfp4w(_ptr(x), _ptr(codes), _ptr(exps), _ptr(bias), _ptr(out), m, n, k,
+                                     max(x.stride(0), k) if m > 1 else k, _ldw(codes), _ldw(exps),
+                                     max(out.stride(0), n), _dtype_code(x), wsp, wsb, _stream(dev))
+    _check(rc, "pli_linear_mxfp4w")
+    return out
+
+
+def gemv_mxfp4w(codes: torch.Tensor, exps: torch.Tensor, x: torch.Tensor,
+                out: torch.Tensor | None = None) -> torch.Tensor:
+    """y = W x over MXFP4 weights (torch.mv semantics): codes [m, k / 2], exps [m, k / 32], x [k] fp16 / bf16"""
+    if x.dim() != 1:
+        raise PliError(f"gemv_mxfp4w expects a 1-D x, got {tuple(x.shape)}")
+    dev = _check_mxfp4w("gemv_mxfp4w", x, [(codes, exps)])
+    x = x.contiguous()
+    m, k = codes.shape[0], x.shape[0]
+    if out is None:
+        out = torch.empty(m, dtype=x.dtype, device=dev)
+    else:
+        _check_out(out, x, (m,), "gemv_mxfp4w")
+    with _on_device(dev):
+        rc = lib().pli_gemv_mxfp4w(_ptr(codes), _ptr(exps), _ptr(x), _ptr(out), m, k, _ldw(codes), _ldw(exps),
+                                   _dtype_code(x), _stream(dev))
+    _check(rc, "pli_gemv_mxfp4w")
+    return out
+
+
+def linear_swiglu_mxfp4w(x: torch.Tensor, g_codes: torch.Tensor, g_exps: torch.Tensor, u_codes: torch.Tensor,
+                         u_exps: torch.Tensor, out: torch.Tensor | None = None,
+                         workspace: torch.Tensor | None = None) -> torch.Tensor:
+    """h = silu(x Wg^T) * (x Wu^T) over MXFP4 gate / up weights in one launch (neither gate nor up is written)"""
+    if x.dim() != 2:
+        raise PliError(f"linear_swiglu_mxfp4w expects a 2-D x, got {tuple(x.shape)}")
+    dev = _check_mxfp4w("linear_swiglu_mxfp4w", x, [(g_codes, g_exps), (u_codes, u_exps)])
+    if x.stride(1) != 1:
+        x = x.contiguous()
+    m, k = x.shape
+    n = g_codes.shape[0]
+    if out is None:
+        out = torch.empty((m, n), dtype=x.dtype, device=dev)
+    else:
+        _check_out(out, x, (m, n), "linear_swiglu_mxfp4w")
+    wsp, wsb = _fp8w_workspace("linear_swiglu_mxfp4w", workspace, dev)
+    with _on_device(dev):
+        rc = lib().pli_linear_swiglu_mxfp4w(_ptr(x), _ptr(g_codes), _ptr(g_exps), _ptr(u_codes), _ptr(u_exps),
+                                            _ptr(out), m, n, k, max(x.stride(0), k) if m > 1 else k, _ldw(g_codes),
+                                            _ldw(g_exps), _ldw(u_codes), _ldw(u_exps), max(out.stride(0), n),
+                                            _dtype_code(x), wsp, wsb, _stream(dev))
+    _check(rc, "pli_linear_swiglu_mxfp4w")
     return out
 
 
