@@ -879,6 +879,58 @@ int pli_gemm_fp8(const void* x8, const float* x_scale, const void* w8,
                  int k, int64_t ldx8, int64_t ldw, int64_t ldc, int dtype,
                  void* stream);
 
+/* MXFP4 weights for prefill (W4A8): an NT GEMM of fp8 e4m3 activation rows
+ * against MXFP4 weights on v_mfma_scale_f32_32x32x64_f8f6f4, the weight's E8M0
+ * block scales fed to the instruction as they are stored.  Nothing is widened
+ * and there is no workspace; pli_linear_mxfp4w is unchanged, a caller opts in
+ * by calling this function.
+ *
+ * Result: C[r, j] = round_T( x_scale[r] * sum_i decode_e4m3(x8[r, i]) *
+ *   decode_e2m1(w4[j, i]) * 2^(w_exp[j, i / 32] - 127)  (+ bias[j]) ).  The sum
+ *   is fp32; x_scale and the bias come after the sum; one rounding to T.
+ * Operands: x8 [m, k] e4m3fn codes (ldx8 in bytes) and x_scale, device fp32
+ *   [m], exactly what pli_quantize_rows_fp8 writes; x_scale may be NULL: all
+ *   ones.  w4 [n, k / 2], w_exp [n, k / 32], ldw and lds (bytes) are exactly
+ *   pli_linear_mxfp4w's: the format is fixed, nothing is re-packed or
+ *   pre-permuted, and w_exp may not be NULL.  T (dtype) is bf16 or fp16 and is
+ *   the type of C (ldc in elements) and bias.  k % 32 == 0 on every route.
+ *   Scales and codes are read on the device: a captured call replays while
+ *   they change in place.  Nothing is allocated or synchronised.
+ * Scale contract of this call: every scale byte has s - 127 in [-96, 96], for
+ *   both output types.  Then every term code x code x 2^e lies in [2^-106,
+ *   2688 * 2^96], a normal fp32 number of at most 6 significant bits, and a sum
+ *   over k <= 2^16 cannot overflow unless the true sum does.  Outside the
+ *   contract the outputs of that weight row are unspecified, but no access
+ *   leaves an operand.  The Python quantize_weight_mxfp4 writes a scale
+ *   outside +-96 only for a block whose absmax is outside about 2^+-94 (its
+ *   rule is e = floor(log2(absmax)) - 2).
+ * NaN: a 0xFF scale byte makes exactly the outputs of its row j NaN, in all m
+ *   rows, on every route; a NaN code in x8 makes exactly its row r NaN.
+ * Routes, in this order, from host arguments only (csrc/mxfp4a_plan.h;
+ *   pli_last_route names the kernel):
+ *   1. m == 0 or n == 0: nothing, and the operands may be NULL; k == 0:
+ *      C = bias or 0 ("gemm_mxfp4_generic").
+ *   2. "gemm_mxfp4_mx": m >= 17, k % 128 == 0, x8 / w4 16-byte aligned, ldx8
+ *      and ldw % 16 == 0, w_exp 4-byte aligned and lds % 4 == 0 (a lane loads
+ *      the four scale bytes of a K-step as one dword), n and ldc % 4 == 0, c
+ *      8-byte aligned.  gemm_fp8_mx's 128 x 128 tile and X side; the W image
+ *      is 64 bytes per row and K-step, two 24 KiB LDS stages; e2m1 operands
+ *      are four registers (cbsz = 4); ragged m / n edges by clamped loads and
+ *      masked stores.  The order in which the instruction sums its 64 terms
+ *      is its own, so this route agrees with route 3 to fp32 rounding, and
+ *      bitwise wherever every partial sum is exact.
+ *   3. "gemm_mxfp4_generic": one thread per output, fp32 fma in k order, any
+ *      shape, leading dimension and alignment.
+ * PLI_EINVAL before any HIP call, in this order: a dtype other than fp16 /
+ *   bf16, a negative shape, k % 32 != 0, a leading dimension below its width
+ *   (ldx8 >= k, ldw >= k / 2, lds >= k / 32, ldc >= n), a NULL operand of a
+ *   non-empty call (w_exp included; x_scale and bias may be NULL), a grid too
+ *   large. */
+int pli_gemm_mxfp4(const void* x8, const float* x_scale, const void* w4,
+                   const void* w_exp, const void* bias, void* c, int m, int n,
+                   int k, int64_t ldx8, int64_t ldw, int64_t lds, int64_t ldc,
+                   int dtype, void* stream);
+
 /* Next-token sampling on the device: temperature, top-k, top-p and the draw of
  * ch02/generation.py:23-31 (temperature, top-k, multinomial),
  * ch02/cached_generation.py:245,265 (temperature) and ch10/engine.py:96-115

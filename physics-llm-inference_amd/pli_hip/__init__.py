@@ -130,6 +130,8 @@ _SIGS = {
     # fp8 activations (W8A8): the row quantiser and the codes x codes NT GEMM
     "pli_quantize_rows_fp8": [_vp, _c_i64, _vp, _c_i64, _vp, _c_int, _c_int, _c_int, _vp],
     "pli_gemm_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_int, _vp],
+    "pli_gemm_mxfp4": [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int,
+                       _vp],
     # next-token sampling: logits, ld, rows, vocab, dtype, temperature, top_k, top_p, uniforms, seed, offset_dev,
     # offset_add, tokens, ld_tokens, workspace, workspace_bytes, stream
     "pli_sample_workspace_size": [_c_int] * 3,
@@ -1568,6 +1570,84 @@ def linear_fp8a(x: torch.Tensor, w8: torch.Tensor, w_scale: torch.Tensor | None,
         raise PliError("HIP path called with a CPU tensor")
     x8, x_scale = quantize_rows_fp8(x)
     return gemm_fp8(x8, x_scale, w8, w_scale, bias=bias, out_dtype=x.dtype, out=out)
+
+
+# ------------------------------------------------- MXFP4 weights x fp8 activations (W4A8)
+MXFP4A_EXP_RANGE = (-96, 96)  # the scale contract of pli_gemm_mxfp4: s - 127 of every scale byte, both output types
+
+
+def _check_mxfp4a(what: str, x8: torch.Tensor, x_scale, codes, exps) -> torch.device:
+    """x8 [m, k] fp8 codes and x_scale as _check_fp8a takes them; codes uint8 [n, k / 2] and exps uint8 [n, k / 32]
+    as _check_mxfp4w takes them"""
+    if not x8.is_cuda:
+        raise PliError("HIP path called with a CPU tensor")
+    dev = x8.device
+    if x8.dim() != 2:
+        raise PliError(f"{what} expects a 2-D x8, got {tuple(x8.shape)}")
+    if x8.dtype not in FP8_POOL_DTYPES:
+        raise PliError(f"{what}: x8 must be a torch.float8_e4m3fn or torch.uint8 tensor on {dev}, got {x8.dtype}")
+    if x8.numel() and x8.stride(1) != 1:
+        raise PliError(f"{what}: x8 needs a unit column stride (the codes are used in place)")
+    m, k = x8.shape
+    if x_scale is not None and (not x_scale.is_cuda or x_scale.device != dev or x_scale.dtype != torch.float32 or
+                                tuple(x_scale.shape) != (m,) or not x_scale.is_contiguous()):
+        raise PliError(f"{what}: x_scale must be None or a contiguous fp32 [{m}] tensor on {dev}")
+    if k % MXFP4_BLOCK:
+        raise PliError(f"{what}: k = {k} is not a multiple of the MX block of 32")
+    for t, name, width in ((codes, "codes", k // 2), (exps, "exps", k // MXFP4_BLOCK)):
+        if not isinstance(t, torch.Tensor):
+            raise PliError(f"{what}: {name} must be a tensor, got {type(t).__name__} (the scale bytes have no default)")
+        if not t.is_cuda:
+            raise PliError("HIP path called with a CPU tensor")
+        if t.device != dev or t.dtype != torch.uint8:
+            raise PliError(f"{what}: {name} must be a torch.uint8 tensor on {dev}, got {t.dtype} on {t.device}")
+        if t.dim() != 2 or t.shape[0] != codes.shape[0] or t.shape[1] != width:
+            raise PliError(f"{what} shape mismatch: x8{tuple(x8.shape)} {name}{tuple(t.shape)}")
+        if t.numel() and t.stride(1) != 1:
+            raise PliError(f"{what}: {name} need a unit column stride (they are used in place)")
+    return dev
+
+
+def gemm_mxfp4(x8: torch.Tensor, x_scale: torch.Tensor | None, codes: torch.Tensor, exps: torch.Tensor,
+               bias: torch.Tensor | None = None, out: torch.Tensor | None = None,
+               out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """C = (x_scale[:, None] * decode(x8)) W^T (+ bias) with W = dequantize_weight_mxfp4(codes, exps): x8 [m, k]
+    e4m3fn codes and x_scale fp32 [m] or None (ones) as quantize_rows_fp8 writes them, codes uint8 [n, k / 2] and exps
+    uint8 [n, k / 32] as linear_mxfp4w takes them (any row stride, used in place); C and bias ``out_dtype`` (bf16 /
+    fp16).  fp32 sum, x_scale and bias after the sum, one rounding.  Every scale byte within MXFP4A_EXP_RANGE of 127."""
+    dev = _check_mxfp4a("gemm_mxfp4", x8, x_scale, codes, exps)
+    if out_dtype not in (torch.float16, torch.bfloat16):
+        raise PliError(f"gemm_mxfp4: out_dtype must be fp16 or bf16, got {out_dtype}")
+    m, k = x8.shape
+    n = codes.shape[0]
+    if bias is not None:
+        if not bias.is_cuda or bias.device != dev or bias.dtype != out_dtype or tuple(bias.shape) != (n,):
+            raise PliError(f"gemm_mxfp4: bias must be a {out_dtype} [{n}] tensor on {dev}")
+        bias = bias.contiguous()
+    if out is None:
+        out = torch.empty((m, n), dtype=out_dtype, device=dev)
+    else:
+        if out.dtype != out_dtype:
+            raise PliError(f"gemm_mxfp4: out is {out.dtype}, out_dtype {out_dtype}")
+        _check_out(out, out, (m, n), "gemm_mxfp4")
+        if out.device != dev:
+            raise PliError(f"tensors on different devices: {out.device} vs {dev}")
+    with _on_device(dev):
+        rc = lib().pli_gemm_mxfp4(_ptr(x8), _ptr(x_scale), _ptr(codes), _ptr(exps), _ptr(bias), _ptr(out), m, n, k,
+                                  _ldw(x8), _ldw(codes), _ldw(exps), max(out.stride(0), n), DTYPE_CODE[out_dtype],
+                                  _stream(dev))
+    _check(rc, "pli_gemm_mxfp4")
+    return out
+
+
+def linear_mxfp4a(x: torch.Tensor, codes: torch.Tensor, exps: torch.Tensor, bias: torch.Tensor | None = None,
+                  out: torch.Tensor | None = None) -> torch.Tensor:
+    """x W^T (+ bias) over MXFP4 weights with the activations in fp8: quantize_rows_fp8(x), then gemm_mxfp4 (the
+    sibling of linear_fp8a; no workspace); the result has x's dtype.  Bitwise the two calls."""
+    if not x.is_cuda:
+        raise PliError("HIP path called with a CPU tensor")
+    x8, x_scale = quantize_rows_fp8(x)
+    return gemm_mxfp4(x8, x_scale, codes, exps, bias=bias, out=out, out_dtype=x.dtype)
 
 
 def _rms_gemm_fp8w(a: torch.Tensor, norm_weight: torch.Tensor, eps: float, groups: list,
