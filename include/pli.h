@@ -931,6 +931,62 @@ int pli_gemm_mxfp4(const void* x8, const float* x_scale, const void* w4,
                    int k, int64_t ldx8, int64_t ldw, int64_t lds, int64_t ldc,
                    int dtype, void* stream);
 
+/* Few rows over fp8 or MXFP4 weights: pli_gemm_fp8 / pli_gemm_mxfp4 with a
+ * caller-owned device workspace, for calls of 17 .. 256 rows.  Such a call is
+ * one or two rows of 128 x 128 tiles, far fewer workgroups than the device has
+ * CUs; with a workspace K is cut into S chunks, every (n tile, chunk, m tile)
+ * is a workgroup, and a second kernel sums the fp32 partials.
+ *
+ * Semantics: pli_gemm_fp8_ws is pli_gemm_fp8 and pli_gemm_mxfp4_ws is
+ *   pli_gemm_mxfp4 in every respect: operands, scales, what may be NULL, the NaN
+ *   rules, the MXFP4 scale contract, fp32 sum, one rounding to T, everything
+ *   read on the device (a captured call replays while its operands change in
+ *   place).  The partials are summed in chunk order without atomics, so a call
+ *   gives the same bits every time; against the plain call the sum has one
+ *   more order, so the two agree to fp32 rounding, and bitwise wherever every
+ *   partial sum is exact.  Nothing is allocated or synchronised; the workspace
+ *   is scratch, nothing persists between calls.
+ * Arguments: the plain call's, then after dtype the workspace (16-byte
+ *   aligned), its size in bytes and `splits`, as pli_gemm_ws places its
+ *   workspace.  splits == 0: the rule below chooses S; splits >= 1: S is
+ *   forced, at most k / 128 and 16.
+ * Split rule (csrc/mx_splitk_plan.h), ks = k / 128, tiles = ceil(n / 128) *
+ *   ceil(m / 128): S = the smallest count with tiles * S >= 256, at most 16 and
+ *   at most ks / 4 (a chunk of the rule keeps four K-steps), and 1 with more
+ *   than 128 tiles (the plain call already covers most of the device); chunk c is K-steps
+ *   [c * ceil(ks / S), min(ks, (c + 1) * ceil(ks / S))), and S is lowered to
+ *   ceil(ks / ceil(ks / S)) so that no chunk is empty.
+ * Routes, from host arguments only (pli_last_route names the kernels):
+ *   1. "gemm_mx_splitk+gemm_mx_splitk_reduce": the plain call's *_mx route
+ *      applies (see above), 17 <= m <= 256, the workspace is not NULL, 16-byte
+ *      aligned and holds S * m * n * 4 bytes, and S >= 2.  The first kernel
+ *      writes fp32 [S][m][n]: per workgroup 128 weight rows x 32 * ceil(min(m,
+ *      128) / 32) activation rows over one chunk, the four waves splitting n,
+ *      so each weight byte goes from memory straight into one lane's operand
+ *      registers, once per call; the activation rows go through three LDS
+ *      stages.  The second sums the partials in order c = 0 .. S - 1, applies
+ *      the plain kernels' finishing expression, the bias and one rounding.
+ *   2. anything else (a NULL, misaligned or too small workspace included): the
+ *      call is the plain entry point, bit for bit, route string and all.
+ * pli_gemm_fp8_workspace_size / pli_gemm_mxfp4_workspace_size(m, n, k, splits):
+ *   S * m * n * 4, the bytes route 1 uses, or 0 where the shape rules it out
+ *   (m outside 17 .. 256, k % 128 != 0, n % 4 != 0, S < 2, splits < 0); the
+ *   pointer conditions are the call's.  The same code decides both.
+ * PLI_EINVAL before any HIP call: the plain call's rules in its order, then
+ *   splits < 0. */
+size_t pli_gemm_fp8_workspace_size(int m, int n, int k, int splits);
+int pli_gemm_fp8_ws(const void* x8, const float* x_scale, const void* w8,
+                    const float* w_scale, const void* bias, void* c, int m,
+                    int n, int k, int64_t ldx8, int64_t ldw, int64_t ldc,
+                    int dtype, void* workspace, size_t workspace_bytes,
+                    int splits, void* stream);
+size_t pli_gemm_mxfp4_workspace_size(int m, int n, int k, int splits);
+int pli_gemm_mxfp4_ws(const void* x8, const float* x_scale, const void* w4,
+                      const void* w_exp, const void* bias, void* c, int m,
+                      int n, int k, int64_t ldx8, int64_t ldw, int64_t lds,
+                      int64_t ldc, int dtype, void* workspace,
+                      size_t workspace_bytes, int splits, void* stream);
+
 /* Next-token sampling on the device: temperature, top-k, top-p and the draw of
  * ch02/generation.py:23-31 (temperature, top-k, multinomial),
  * ch02/cached_generation.py:245,265 (temperature) and ch10/engine.py:96-115

@@ -17,6 +17,7 @@
 //   gemm_fp8_generic  one thread per output through the header codec, anything
 #include "fp8_kv.h"
 #include "fp8a_plan.h"
+#include "mx_finish.h"
 #include "pli_common.h"
 
 namespace pli {
@@ -122,9 +123,8 @@ __global__ __launch_bounds__(kFp8aQuantThreads) void quant_rows_fp8(const uint16
 }
 
 // ---------------------------------------------------------------------------
-// The shared epilogue expression: the two kernels agree bit for bit wherever
-// their sums do.
-__device__ __forceinline__ float fp8a_finish(float sum, float xs, float ws) { return sum * (xs * ws); }
+// The shared epilogue expression, fp8a_finish (mx_finish.h): the two kernels
+// agree bit for bit wherever their sums do.
 
 // ---------------------------------------------------------------------------
 // gemm_fp8_mx: C^T tile [128 n][128 m] = W8 tile x X8 tile^T.  Per K-step of

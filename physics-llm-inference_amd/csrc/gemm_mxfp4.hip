@@ -19,6 +19,7 @@
 //   gemm_mxfp4_generic  one thread per output through the header codecs, anything
 #include "fp4_codec.h"
 #include "fp8_kv.h"
+#include "mx_finish.h"
 #include "mxfp4a_plan.h"
 #include "pli_common.h"
 
@@ -27,9 +28,8 @@ namespace {
 
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 
-// The shared epilogue expression: the two kernels agree bit for bit wherever
-// their sums do.
-__device__ __forceinline__ float mxfp4a_finish(float sum, float xs) { return sum * xs; }
+// The shared epilogue expression, mxfp4a_finish (mx_finish.h): the two kernels
+// agree bit for bit wherever their sums do.
 
 // ---------------------------------------------------------------------------
 // gemm_mxfp4_mx: C^T tile [128 n][128 m] = W4 tile x X8 tile^T.  Per K-step of

@@ -132,6 +132,13 @@ _SIGS = {
     "pli_gemm_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_int, _vp],
     "pli_gemm_mxfp4": [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int,
                        _vp],
+    # the split-K forms for 17 .. 256 rows: the plain signatures plus workspace, workspace_bytes, splits before the stream
+    "pli_gemm_fp8_workspace_size": [_c_int] * 4,
+    "pli_gemm_fp8_ws": [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_int, _vp,
+                        ctypes.c_size_t, _c_int, _vp],
+    "pli_gemm_mxfp4_workspace_size": [_c_int] * 4,
+    "pli_gemm_mxfp4_ws": [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int,
+                          _vp, ctypes.c_size_t, _c_int, _vp],
     # next-token sampling: logits, ld, rows, vocab, dtype, temperature, top_k, top_p, uniforms, seed, offset_dev,
     # offset_add, tokens, ld_tokens, workspace, workspace_bytes, stream
     "pli_sample_workspace_size": [_c_int] * 3,
@@ -1532,12 +1539,20 @@ def _check_fp8a(what: str, x8: torch.Tensor, x_scale, w8: torch.Tensor, w_scale)
     return dev
 
 
+def gemm_fp8_workspace_bytes(m: int, n: int, k: int, splits: int = 0) -> int:
+    """bytes of workspace the split-K route of gemm_fp8 (17 .. 256 rows) uses for [m, k] x [n, k]^T; 0: the shape
+    rules it out and the call is the plain one.  ``splits``: 0 the rule chooses, >= 1 forced."""
+    return int(lib().pli_gemm_fp8_workspace_size(int(m), int(n), int(k), int(splits)))
+
+
 def gemm_fp8(x8: torch.Tensor, x_scale: torch.Tensor | None, w8: torch.Tensor, w_scale: torch.Tensor | None,
              bias: torch.Tensor | None = None, out_dtype: torch.dtype = torch.bfloat16,
-             out: torch.Tensor | None = None) -> torch.Tensor:
+             out: torch.Tensor | None = None, workspace: torch.Tensor | None = None, splits: int = 0) -> torch.Tensor:
     """C = (x_scale[:, None] * decode(x8)) (w_scale[:, None] * decode(w8))^T (+ bias) over two operands of e4m3fn
     codes: x8 [m, k], w8 [n, k] (float8_e4m3fn or uint8, any row stride, used in place), scales fp32 [m] / [n] or None
-    (ones), C and bias ``out_dtype`` (bf16 / fp16).  fp32 sum, scales and bias after the sum, one rounding."""
+    (ones), C and bias ``out_dtype`` (bf16 / fp16).  fp32 sum, scales and bias after the sum, one rounding.
+    ``workspace`` (bytes from gemm_fp8_workspace_bytes) lets a call of 17 .. 256 rows split K over workgroups
+    (pli_gemm_fp8_ws; ``splits`` as there); None is the plain call."""
     dev = _check_fp8a("gemm_fp8", x8, x_scale, w8, w_scale)
     if out_dtype not in (torch.float16, torch.bfloat16):
         raise PliError(f"gemm_fp8: out_dtype must be fp16 or bf16, got {out_dtype}")
@@ -1555,21 +1570,28 @@ def gemm_fp8(x8: torch.Tensor, x_scale: torch.Tensor | None, w8: torch.Tensor, w
         _check_out(out, out, (m, n), "gemm_fp8")
         if out.device != dev:
             raise PliError(f"tensors on different devices: {out.device} vs {dev}")
+    head = (_ptr(x8), _ptr(x_scale), _ptr(w8), _ptr(w_scale), _ptr(bias), _ptr(out), m, n, k, _ldw(x8), _ldw(w8),
+            max(out.stride(0), n), DTYPE_CODE[out_dtype])
     with _on_device(dev):
-        rc = lib().pli_gemm_fp8(_ptr(x8), _ptr(x_scale), _ptr(w8), _ptr(w_scale), _ptr(bias), _ptr(out), m, n, k,
-                                _ldw(x8), _ldw(w8), max(out.stride(0), n), DTYPE_CODE[out_dtype], _stream(dev))
-    _check(rc, "pli_gemm_fp8")
+        if workspace is None:
+            rc = lib().pli_gemm_fp8(*head, _stream(dev))
+        else:
+            rc = lib().pli_gemm_fp8_ws(*head, *_fp8w_workspace("gemm_fp8", workspace, dev), int(splits), _stream(dev))
+    _check(rc, "pli_gemm_fp8" if workspace is None else "pli_gemm_fp8_ws")
     return out
 
 
 def linear_fp8a(x: torch.Tensor, w8: torch.Tensor, w_scale: torch.Tensor | None, bias: torch.Tensor | None = None,
-                out: torch.Tensor | None = None) -> torch.Tensor:
+                out: torch.Tensor | None = None, workspace: torch.Tensor | None = None,
+                splits: int = 0) -> torch.Tensor:
     """x W^T (+ bias) with both operands in fp8: quantize_rows_fp8(x), then gemm_fp8 against the weight codes
-    (W = decode(w8) * w_scale[:, None], as linear_fp8w takes them); the result has x's dtype.  Bitwise the two calls."""
+    (W = decode(w8) * w_scale[:, None], as linear_fp8w takes them); the result has x's dtype.  Bitwise the two calls.
+    ``workspace`` / ``splits`` as for gemm_fp8."""
     if not x.is_cuda:
         raise PliError("HIP path called with a CPU tensor")
     x8, x_scale = quantize_rows_fp8(x)
-    return gemm_fp8(x8, x_scale, w8, w_scale, bias=bias, out_dtype=x.dtype, out=out)
+    return gemm_fp8(x8, x_scale, w8, w_scale, bias=bias, out_dtype=x.dtype, out=out, workspace=workspace,
+                    splits=splits)
 
 
 # ------------------------------------------------- MXFP4 weights x fp8 activations (W4A8)
@@ -1608,13 +1630,21 @@ def _check_mxfp4a(what: str, x8: torch.Tensor, x_scale, codes, exps) -> torch.de
     return dev
 
 
+def gemm_mxfp4_workspace_bytes(m: int, n: int, k: int, splits: int = 0) -> int:
+    """gemm_fp8_workspace_bytes for gemm_mxfp4 (pli_gemm_mxfp4_workspace_size)"""
+    return int(lib().pli_gemm_mxfp4_workspace_size(int(m), int(n), int(k), int(splits)))
+
+
 def gemm_mxfp4(x8: torch.Tensor, x_scale: torch.Tensor | None, codes: torch.Tensor, exps: torch.Tensor,
                bias: torch.Tensor | None = None, out: torch.Tensor | None = None,
-               out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+               out_dtype: torch.dtype = torch.bfloat16, workspace: torch.Tensor | None = None,
+               splits: int = 0) -> torch.Tensor:
     """C = (x_scale[:, None] * decode(x8)) W^T (+ bias) with W = dequantize_weight_mxfp4(codes, exps): x8 [m, k]
     e4m3fn codes and x_scale fp32 [m] or None (ones) as quantize_rows_fp8 writes them, codes uint8 [n, k / 2] and exps
     uint8 [n, k / 32] as linear_mxfp4w takes them (any row stride, used in place); C and bias ``out_dtype`` (bf16 /
-    fp16).  fp32 sum, x_scale and bias after the sum, one rounding.  Every scale byte within MXFP4A_EXP_RANGE of 127."""
+    fp16).  fp32 sum, x_scale and bias after the sum, one rounding.  Every scale byte within MXFP4A_EXP_RANGE of 127.
+    ``workspace`` (bytes from gemm_mxfp4_workspace_bytes) lets a call of 17 .. 256 rows split K over workgroups
+    (pli_gemm_mxfp4_ws; ``splits`` as there); None is the plain call."""
     dev = _check_mxfp4a("gemm_mxfp4", x8, x_scale, codes, exps)
     if out_dtype not in (torch.float16, torch.bfloat16):
         raise PliError(f"gemm_mxfp4: out_dtype must be fp16 or bf16, got {out_dtype}")
@@ -1632,22 +1662,29 @@ def gemm_mxfp4(x8: torch.Tensor, x_scale: torch.Tensor | None, codes: torch.Tens
         _check_out(out, out, (m, n), "gemm_mxfp4")
         if out.device != dev:
             raise PliError(f"tensors on different devices: {out.device} vs {dev}")
+    head = (_ptr(x8), _ptr(x_scale), _ptr(codes), _ptr(exps), _ptr(bias), _ptr(out), m, n, k, _ldw(x8), _ldw(codes),
+            _ldw(exps), max(out.stride(0), n), DTYPE_CODE[out_dtype])
     with _on_device(dev):
-        rc = lib().pli_gemm_mxfp4(_ptr(x8), _ptr(x_scale), _ptr(codes), _ptr(exps), _ptr(bias), _ptr(out), m, n, k,
-                                  _ldw(x8), _ldw(codes), _ldw(exps), max(out.stride(0), n), DTYPE_CODE[out_dtype],
-                                  _stream(dev))
-    _check(rc, "pli_gemm_mxfp4")
+        if workspace is None:
+            rc = lib().pli_gemm_mxfp4(*head, _stream(dev))
+        else:
+            rc = lib().pli_gemm_mxfp4_ws(*head, *_fp8w_workspace("gemm_mxfp4", workspace, dev), int(splits),
+                                         _stream(dev))
+    _check(rc, "pli_gemm_mxfp4" if workspace is None else "pli_gemm_mxfp4_ws")
     return out
 
 
 def linear_mxfp4a(x: torch.Tensor, codes: torch.Tensor, exps: torch.Tensor, bias: torch.Tensor | None = None,
-                  out: torch.Tensor | None = None) -> torch.Tensor:
+                  out: torch.Tensor | None = None, workspace: torch.Tensor | None = None,
+                  splits: int = 0) -> torch.Tensor:
     """x W^T (+ bias) over MXFP4 weights with the activations in fp8: quantize_rows_fp8(x), then gemm_mxfp4 (the
-    sibling of linear_fp8a; no workspace); the result has x's dtype.  Bitwise the two calls."""
+    sibling of linear_fp8a); the result has x's dtype.  Bitwise the two calls.  ``workspace`` / ``splits`` as for
+    gemm_mxfp4."""
     if not x.is_cuda:
         raise PliError("HIP path called with a CPU tensor")
     x8, x_scale = quantize_rows_fp8(x)
-    return gemm_mxfp4(x8, x_scale, codes, exps, bias=bias, out=out, out_dtype=x.dtype)
+    return gemm_mxfp4(x8, x_scale, codes, exps, bias=bias, out=out, out_dtype=x.dtype, workspace=workspace,
+                      splits=splits)
 
 
 def _rms_gemm_fp8w(a: torch.Tensor, norm_weight: torch.Tensor, eps: float, groups: list,
