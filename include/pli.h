@@ -987,6 +987,59 @@ int pli_gemm_mxfp4_ws(const void* x8, const float* x_scale, const void* w4,
                       int64_t ldc, int dtype, void* workspace,
                       size_t workspace_bytes, int splits, void* stream);
 
+/* MXFP4 expert weights: pli_gemm_grouped over fp8 activation rows and every
+ * expert's weight in pli_gemm_mxfp4's format (W4A8), for the MoE layer.
+ *
+ * Semantics: for every expert e and sorted row r in [offsets[e],
+ *   offsets[e + 1]), t = gather ? gather[r] : r:
+ *     c[r, j] = round_T( x_scale[t] * sum_i decode_e4m3(x8[t, i]) *
+ *               decode_e2m1(w4_e[j, i]) * 2^(w_exp_e[j, i / 32] - 127) ),
+ *   the sum in fp32 and one rounding; or, with the up tables (fused SwiGLU, W1
+ *   in w4 / wexp and W3 in wu4 / wuexp), g and u those two finished fp32
+ *   values, c[r, j] = round_T(silu(g) * u): SiLU and the product in fp32, one
+ *   rounding, the rule of pli_gemm_grouped.
+ * Operands: x8 [tokens, k] and x_scale [tokens] as pli_quantize_rows_fp8
+ *   writes them (x_scale NULL: ones); w4_ptrs / wexp_ptrs (and wu4_ptrs /
+ *   wuexp_ptrs: both or neither) are DEVICE arrays of the experts' code and
+ *   scale-byte pointers, each expert [n, k / 2] and [n, k / 32] with the common
+ *   leading dimensions ldw / lds (bytes), entries 16-byte (codes) and 4-byte
+ *   (scale bytes) aligned; offsets [experts + 1] and gather as pli_moe_route
+ *   writes them.  rows_bound >= offsets[experts], the number of sorted rows (a
+ *   host value: it also bounds every expert's rows, picks the kernel and sizes
+ *   its grid; a smaller value leaves rows unwritten); c holds rows_bound rows
+ *   of n elements of T (bf16 / fp16, ldc in elements).  k % 32 == 0.
+ *   The scale contract and the NaN rules are pli_gemm_mxfp4's: a 0xFF scale
+ *   byte of expert e's row j makes exactly column j of e's rows NaN, a NaN code
+ *   in token t's row exactly the sorted rows that gather t.  No atomics, no
+ *   workspace, nothing allocated or synchronised; offsets, gather, tables,
+ *   codes and scales are read on the device, so a captured call replays.
+ * Routes, from host arguments only (csrc/grouped_mxfp4_plan.h; pli_last_route
+ *   names the kernel):
+ *   1. rows_bound == 0 or n == 0: nothing, and the operands may be NULL.
+ *   2. "gemm_grouped_mxfp4": k % 128 == 0 (k > 0), n % 16 == 0, x8 16-byte
+ *      aligned, ldx8 and ldw % 16 == 0, lds % 4 == 0, ldc % 4 == 0, c 8-byte
+ *      aligned, ceil(rows_bound / 128) + experts <= 65535.  One workgroup per
+ *      (128 weight rows, slot of 128 sorted rows); a slot finds its (expert,
+ *      slab) by a scan of offsets.  Each wave loads its 32 weight rows (SwiGLU:
+ *      of both matrices) straight into operand registers; the gathered
+ *      activation rows go through three LDS stages; 32 * ceil(min(rows_bound,
+ *      128) / 32) rows are multiplied per slab.
+ *   3. "gemm_grouped_mxfp4_generic": one thread per output element, fp32 fma
+ *      in k order, any shape, leading dimension and alignment (k == 0: zeros).
+ * PLI_EINVAL before any HIP call, in this order: a dtype other than fp16 /
+ *   bf16; experts < 1 or a negative shape; k % 32 != 0; a leading dimension
+ *   below its width (ldx8 >= k, ldw >= k / 2, lds >= k / 32, ldc >= n); then,
+ *   for a non-empty call, a NULL c, offsets, x8 or table (x_scale and gather
+ *   may be NULL); one up table without the other; a grid too large. */
+int pli_gemm_grouped_mxfp4(const void* x8, const float* x_scale,
+                           const int32_t* gather, const void* const* w4_ptrs,
+                           const void* const* wexp_ptrs,
+                           const void* const* wu4_ptrs,
+                           const void* const* wuexp_ptrs, void* c,
+                           const int32_t* offsets, int experts, int rows_bound,
+                           int n, int k, int64_t ldx8, int64_t ldw, int64_t lds,
+                           int64_t ldc, int dtype, void* stream);
+
 /* Next-token sampling on the device: temperature, top-k, top-p and the draw of
  * ch02/generation.py:23-31 (temperature, top-k, multinomial),
  * ch02/cached_generation.py:245,265 (temperature) and ch10/engine.py:96-115

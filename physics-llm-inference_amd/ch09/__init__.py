@@ -18,6 +18,7 @@ from .moe_layer import (
     expert_load_balance_loss,
     explain_moe,
 )
+from .mxfp4_moe import Mxfp4MoELayer
 from .nccl_primitives import (
     AllGatherConfig,
     AllReduceConfig,
@@ -41,6 +42,7 @@ __all__ = [
     "Router",
     "ExpertLayer",
     "MoELayer",
+    "Mxfp4MoELayer",
     "expert_load_balance_loss",
     "explain_moe",
     "MoEInferenceEngine",

@@ -132,6 +132,7 @@ _SIGS = {
     "pli_gemm_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_int, _vp],
     "pli_gemm_mxfp4": [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int,
                        _vp],
+    "pli_gemm_grouped_mxfp4": [_vp] * 9 + [_c_int] * 4 + [_c_i64] * 4 + [_c_int, _vp],
     # the split-K forms for 17 .. 256 rows: the plain signatures plus workspace, workspace_bytes, splits before the stream
     "pli_gemm_fp8_workspace_size": [_c_int] * 4,
     "pli_gemm_fp8_ws": [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_int, _vp,
@@ -1685,6 +1686,95 @@ def linear_mxfp4a(x: torch.Tensor, codes: torch.Tensor, exps: torch.Tensor, bias
     x8, x_scale = quantize_rows_fp8(x)
     return gemm_mxfp4(x8, x_scale, codes, exps, bias=bias, out=out, out_dtype=x.dtype, workspace=workspace,
                       splits=splits)
+
+
+# ------------------------------------------------- MXFP4 expert weights (grouped W4A8)
+class Mxfp4Tables:
+    """The device pointer tables of a list of experts' MXFP4 weights: ``codes`` / ``exps`` int64 [E] (the data
+    pointers pli_gemm_grouped_mxfp4 reads), the common shape ``n`` / ``k`` and leading dimensions ``ldw`` / ``lds``,
+    and the weight tensors themselves (``weights``), which live as long as the tables do."""
+
+    def __init__(self, weights):
+        weights = [(c, e) for c, e in weights]
+        if not weights:
+            raise PliError("mxfp4_weight_tables: no experts")
+        c0, e0 = weights[0]
+        for c, e in weights:
+            for t in (c, e):
+                if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                    raise PliError("HIP path called with a CPU tensor")
+                if t.device != c0.device or t.dtype != torch.uint8 or t.dim() != 2 or (t.numel() and t.stride(1) != 1):
+                    raise PliError(f"mxfp4_weight_tables: codes and exps must be 2-D torch.uint8 tensors on "
+                                   f"{c0.device} with a unit column stride")
+            if (tuple(c.shape) != tuple(c0.shape) or tuple(e.shape) != tuple(e0.shape) or _ldw(c) != _ldw(c0) or
+                    _ldw(e) != _ldw(e0) or c.shape[0] != e.shape[0] or c.shape[1] != 16 * e.shape[1]):
+                raise PliError("mxfp4_weight_tables: every expert needs codes [n, k / 2] and exps [n, k / 32] of one "
+                               "shape and one pair of row strides")
+            if c.data_ptr() % 16 or e.data_ptr() % 4:
+                raise PliError("mxfp4_weight_tables: codes must be 16-byte and exps 4-byte aligned")
+        self.weights = weights
+        self.n, self.k, self.ldw, self.lds = c0.shape[0], 2 * c0.shape[1], _ldw(c0), _ldw(e0)
+        self.codes = torch.tensor([c.data_ptr() for c, _ in weights], dtype=torch.int64, device=c0.device)
+        self.exps = torch.tensor([e.data_ptr() for _, e in weights], dtype=torch.int64, device=c0.device)
+
+    def __iter__(self):
+        return iter((self.codes, self.exps))
+
+
+def mxfp4_weight_tables(weights) -> Mxfp4Tables:
+    """``weights``: one (codes uint8 [n, k / 2], exps uint8 [n, k / 32]) per expert, as quantize_weight_mxfp4 writes
+    them, all of one shape and row stride on one device.  Returns the two device pointer tables (``codes, exps =
+    tables``) for gemm_grouped_mxfp4; the object keeps the weight tensors alive."""
+    return Mxfp4Tables(weights)
+
+
+def gemm_grouped_mxfp4(x8: torch.Tensor, x_scale: torch.Tensor | None, gather: torch.Tensor | None,
+                       tables: Mxfp4Tables, offsets: torch.Tensor, rows: int, n: int, k: int,
+                       up_tables: Mxfp4Tables | None = None, out: torch.Tensor | None = None,
+                       out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """Per-expert W4A8 GEMM over expert-sorted rows (pli_gemm_grouped_mxfp4): out[r] = x_scale[t] decode(x8[t])
+    W_e^T, t = gather[r] (None: r), for r in expert e's range of ``offsets``, W_e the expert's MXFP4 weight of
+    ``tables``; with ``up_tables`` silu(. W1_e^T) * (. W3_e^T), SiLU and product in fp32, one rounding.  x8 [tokens,
+    k] / x_scale as quantize_rows_fp8 writes them.  ``rows`` is the host bound rows_bound >= offsets[experts], the
+    number of sorted rows (tokens * top_k after moe_route); ``out``, if given, holds that many rows of ``out_dtype``.
+    ``gather`` (or, without it, x8) holds offsets[experts] rows: a device value, so it is the caller's contract."""
+    if not x8.is_cuda:
+        raise PliError("HIP path called with a CPU tensor")
+    dev = x8.device
+    if x8.dim() != 2 or x8.dtype not in FP8_POOL_DTYPES or (x8.numel() and x8.stride(1) != 1):
+        raise PliError("gemm_grouped_mxfp4: x8 must be a 2-D float8_e4m3fn / uint8 tensor with a unit column stride")
+    if out_dtype not in (torch.float16, torch.bfloat16):
+        raise PliError(f"gemm_grouped_mxfp4: out_dtype must be fp16 or bf16, got {out_dtype}")
+    if x_scale is not None and (x_scale.device != dev or x_scale.dtype != torch.float32 or
+                                tuple(x_scale.shape) != (x8.shape[0],) or not x_scale.is_contiguous()):
+        raise PliError(f"gemm_grouped_mxfp4: x_scale must be None or a contiguous fp32 [{x8.shape[0]}] tensor on {dev}")
+    E = offsets.numel() - 1
+    if E < 1:
+        raise PliError("gemm_grouped_mxfp4: offsets needs experts + 1 >= 2 entries")
+    for t in (tables, up_tables):
+        if t is not None and (len(t.weights) != E or (t.n, t.k) != (n, k) or t.codes.device != dev or
+                              (t.ldw, t.lds) != (tables.ldw, tables.lds)):
+            raise PliError(f"gemm_grouped_mxfp4: tables of {len(t.weights)} experts [{t.n}, {t.k}] do not match "
+                           f"{E} experts [{n}, {k}] on {dev}")
+    if x8.shape[1] != k:
+        raise PliError(f"gemm_grouped_mxfp4 shape mismatch: x8{tuple(x8.shape)} k={k}")
+    for t, name in ((gather, "gather"), (offsets, "offsets")):
+        if t is not None and (t.device != dev or t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous()):
+            raise PliError(f"gemm_grouped_mxfp4: {name} must be a contiguous 1-D int32 tensor on {dev}")
+    if out is None:
+        out = torch.empty(max(rows, 1), n, device=dev, dtype=out_dtype)
+    elif (out.dtype != out_dtype or out.device != dev or out.dim() != 2 or out.shape[0] < rows or out.shape[1] != n or
+          (out.numel() and out.stride(1) != 1)):
+        raise PliError(f"gemm_grouped_mxfp4: out must be a {out_dtype} [>= {rows}, {n}] tensor on {dev} with a unit "
+                       "column stride")
+    up = (None, None) if up_tables is None else (up_tables.codes, up_tables.exps)
+    with _on_device(dev):
+        rc = lib().pli_gemm_grouped_mxfp4(_ptr(x8), _ptr(x_scale), _ptr(gather), _ptr(tables.codes), _ptr(tables.exps),
+                                          _ptr(up[0]), _ptr(up[1]), _ptr(out), _ptr(offsets), E, int(rows), int(n),
+                                          int(k), _ldw(x8), tables.ldw, tables.lds, max(out.stride(0), n),
+                                          DTYPE_CODE[out_dtype], _stream(dev))
+    _check(rc, "pli_gemm_grouped_mxfp4")
+    return out
 
 
 def _rms_gemm_fp8w(a: torch.Tensor, norm_weight: torch.Tensor, eps: float, groups: list,
