@@ -1040,6 +1040,67 @@ int pli_gemm_grouped_mxfp4(const void* x8, const float* x_scale,
                            int n, int k, int64_t ldx8, int64_t ldw, int64_t lds,
                            int64_t ldc, int dtype, void* stream);
 
+/* MoE decode over MXFP4 expert weights: pli_gemm_grouped_mxfp4 with a
+ * caller-owned device workspace, for calls of at most 32 sorted rows (1 .. 16
+ * tokens at top-2).  Such a call only streams the weights of the few experts
+ * that have rows; the plain call gives each of them ceil(n / 128) workgroups
+ * that walk K alone.  With a workspace K is cut into S chunks, every (128
+ * weight rows, chunk, expert) is a workgroup that has the weight loads of its
+ * whole chunk in flight before its first MFMA, and a second kernel sums the
+ * fp32 partials.
+ *
+ * Semantics: pli_gemm_grouped_mxfp4 in every respect: operands, what may be
+ *   NULL, the MXFP4 scale contract, the NaN rules, rows_bound (rows from
+ *   offsets[experts] up to rows_bound stay unwritten), fp32 sum, SiLU and the
+ *   product in fp32, one rounding; offsets, gather, tables, codes and scales
+ *   are read on the device (a captured call replays while they change in
+ *   place).  The partials are summed in chunk order without atomics, so a call
+ *   gives the same bits every time; against the plain call the sum has one
+ *   more order, so the two agree to fp32 rounding, and bitwise wherever every
+ *   partial sum is exact.  Nothing is allocated or synchronised; the workspace
+ *   is scratch.
+ * Arguments: the plain call's up to dtype, then the workspace (16-byte
+ *   aligned), its size in bytes and `splits`.  splits == 0: the rule below
+ *   chooses S; splits >= 1: S is forced, at most k / 128 and 16.
+ * Split rule (csrc/grouped_mxfp4_splitk_plan.h), ks = k / 128, tiles =
+ *   ceil(n / 128): S = the smallest count with tiles * S >= 512 (per expert:
+ *   the host does not know how many experts have rows, and as few as two can),
+ *   at most 16 and at most ks / 4; chunk c is K-steps [c * ceil(ks / S),
+ *   min(ks, (c + 1) * ceil(ks / S))), and S is lowered to ceil(ks / ceil(ks /
+ *   S)) so that no chunk is empty.
+ * Routes, from host arguments only (pli_last_route names the kernels):
+ *   1. "gemm_grouped_mxfp4_splitk+gemm_grouped_mxfp4_splitk_reduce": the
+ *      plain call's "gemm_grouped_mxfp4" route applies (see above), 1 <=
+ *      rows_bound <= 32, experts <= 65535, the workspace is not NULL, 16-byte
+ *      aligned and large enough, and S >= 2.  The first kernel writes fp32
+ *      [S][rows_bound][n] ([S][rows_bound][2][n] with the up tables: gate,
+ *      then up), only rows inside an expert's range; an expert without rows
+ *      reads nothing, its table entries included.  The second sums the
+ *      partials in order c = 0 .. S - 1 and applies the plain kernel's
+ *      epilogue.
+ *   2. anything else (a NULL, misaligned or too small workspace included): the
+ *      call is the plain entry point, bit for bit, route string and all.
+ * pli_gemm_grouped_mxfp4_workspace_size(experts, rows_bound, n, k, swiglu,
+ *   splits): S * rows_bound * n * (1 + swiglu) * 4, the bytes route 1 uses,
+ *   or 0 where the shape rules it out (rows_bound outside 1 .. 32, experts
+ *   outside 1 .. 65535, k % 128 != 0, n % 16 != 0, S < 2, splits < 0); the
+ *   pointer and leading-dimension conditions are the call's.  The same code
+ *   decides both.
+ * PLI_EINVAL before any HIP call: the plain call's rules in its order, then
+ *   splits < 0. */
+size_t pli_gemm_grouped_mxfp4_workspace_size(int experts, int rows_bound, int n,
+                                             int k, int swiglu, int splits);
+int pli_gemm_grouped_mxfp4_ws(const void* x8, const float* x_scale,
+                              const int32_t* gather, const void* const* w4_ptrs,
+                              const void* const* wexp_ptrs,
+                              const void* const* wu4_ptrs,
+                              const void* const* wuexp_ptrs, void* c,
+                              const int32_t* offsets, int experts,
+                              int rows_bound, int n, int k, int64_t ldx8,
+                              int64_t ldw, int64_t lds, int64_t ldc, int dtype,
+                              void* workspace, size_t workspace_bytes,
+                              int splits, void* stream);
+
 /* Next-token sampling on the device: temperature, top-k, top-p and the draw of
  * ch02/generation.py:23-31 (temperature, top-k, multinomial),
  * ch02/cached_generation.py:245,265 (temperature) and ch10/engine.py:96-115

@@ -14,6 +14,10 @@ bits per weight) and keeps the router as it is.  On a ROCm device the forward pa
 On the CPU, and for shapes the grouped kernel's route does not take, the same arithmetic runs in torch over
 ``dequantize_weight_mxfp4`` and the torch form of the row quantiser: fp32 sums, the row scale after the sum, SiLU and
 product in fp32, one rounding per stage.  ``MoELayer`` itself is unchanged.
+
+``from_layer(..., split_decode=True)`` is for decode: with at most 32 sorted rows (16 tokens at top-2) both grouped
+calls get one cached workspace and run ``pli_gemm_grouped_mxfp4_ws``, which splits every expert's K over workgroups.
+Above 32 rows, on the CPU and with the option off (the default) nothing changes.
 """
 from __future__ import annotations
 
@@ -36,12 +40,31 @@ class Mxfp4MoELayer(nn.Module):
                 self.register_buffer(f"{name}_codes_{e}", codes)
                 self.register_buffer(f"{name}_exps_{e}", exps)
         self._tables = None  # (pointer key, w1 tables, w3 tables, w2 tables)
+        self.split_decode = False  # up to SPLIT_ROWS sorted rows: both grouped calls split K over a cached workspace
+        self._workspace = None
+
+    SPLIT_ROWS = 32  # pli_gemm_grouped_mxfp4_ws's row bound
 
     @classmethod
-    def from_layer(cls, layer: MoELayer, dtype: torch.dtype = torch.bfloat16) -> "Mxfp4MoELayer":
+    def from_layer(cls, layer: MoELayer, dtype: torch.dtype = torch.bfloat16,
+                   split_decode: bool = False) -> "Mxfp4MoELayer":
         q = lambda lin: pli_hip.quantize_weight_mxfp4(lin.weight, dtype)  # noqa: E731
-        return cls(layer.config, layer.router, [q(e.w1) for e in layer.experts], [q(e.w3) for e in layer.experts],
-                   [q(e.w2) for e in layer.experts])
+        new = cls(layer.config, layer.router, [q(e.w1) for e in layer.experts], [q(e.w3) for e in layer.experts],
+                  [q(e.w2) for e in layer.experts])
+        new.split_decode = split_decode
+        return new
+
+    def _split_workspace(self, rows: int, device) -> torch.Tensor | None:
+        """one workspace for both grouped calls, sized for SPLIT_ROWS rows over the larger of the two; None above
+        SPLIT_ROWS rows and with the option off: the plain calls"""
+        if not self.split_decode or rows > self.SPLIT_ROWS:
+            return None
+        if self._workspace is None or self._workspace.device != device:
+            c = self.config
+            need = max(pli_hip.gemm_grouped_mxfp4_workspace_bytes(c.num_experts, self.SPLIT_ROWS, n, k, swiglu=sw)
+                       for n, k, sw in ((c.expert_dim, c.hidden_dim, True), (c.hidden_dim, c.expert_dim, False)))
+            self._workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=device)
+        return self._workspace
 
     def _weights(self, name: str):
         return [(getattr(self, f"{name}_codes_{e}"), getattr(self, f"{name}_exps_{e}"))
@@ -66,12 +89,13 @@ class Mxfp4MoELayer(nn.Module):
         w, _, pos, gather, offsets = pli_hip.moe_route(logits, k, c.normalize_expert_weights)
         t1, t3, t2 = self._weight_tables()
         rows = T * k
+        ws = self._split_workspace(rows, x_flat.device)
         x8, xs = pli_hip.quantize_rows_fp8(x_flat)
         h = pli_hip.gemm_grouped_mxfp4(x8, xs, gather, t1, offsets, rows, c.expert_dim, c.hidden_dim, up_tables=t3,
-                                       out_dtype=x_flat.dtype)
+                                       out_dtype=x_flat.dtype, workspace=ws)
         h8, hs = pli_hip.quantize_rows_fp8(h)
         y = pli_hip.gemm_grouped_mxfp4(h8, hs, None, t2, offsets, rows, c.hidden_dim, c.expert_dim,
-                                       out_dtype=x_flat.dtype)
+                                       out_dtype=x_flat.dtype, workspace=ws)
         return pli_hip.moe_combine(y, pos, w, T)
 
     def _route_torch(self, x_flat: torch.Tensor):

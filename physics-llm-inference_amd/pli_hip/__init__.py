@@ -133,6 +133,8 @@ _SIGS = {
     "pli_gemm_mxfp4": [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int,
                        _vp],
     "pli_gemm_grouped_mxfp4": [_vp] * 9 + [_c_int] * 4 + [_c_i64] * 4 + [_c_int, _vp],
+    "pli_gemm_grouped_mxfp4_workspace_size": [_c_int] * 6,
+    "pli_gemm_grouped_mxfp4_ws": [_vp] * 9 + [_c_int] * 4 + [_c_i64] * 4 + [_c_int, _vp, ctypes.c_size_t, _c_int, _vp],
     # the split-K forms for 17 .. 256 rows: the plain signatures plus workspace, workspace_bytes, splits before the stream
     "pli_gemm_fp8_workspace_size": [_c_int] * 4,
     "pli_gemm_fp8_ws": [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_int, _vp,
@@ -1728,16 +1730,27 @@ def mxfp4_weight_tables(weights) -> Mxfp4Tables:
     return Mxfp4Tables(weights)
 
 
+def gemm_grouped_mxfp4_workspace_bytes(experts: int, rows: int, n: int, k: int, swiglu: bool = False,
+                                       splits: int = 0) -> int:
+    """bytes of workspace with which gemm_grouped_mxfp4 splits K for ``rows`` <= 32 sorted rows
+    (pli_gemm_grouped_mxfp4_workspace_size; ``swiglu``: with up_tables); 0: the shape always runs the plain call"""
+    return int(lib().pli_gemm_grouped_mxfp4_workspace_size(int(experts), int(rows), int(n), int(k), int(bool(swiglu)),
+                                                           int(splits)))
+
+
 def gemm_grouped_mxfp4(x8: torch.Tensor, x_scale: torch.Tensor | None, gather: torch.Tensor | None,
                        tables: Mxfp4Tables, offsets: torch.Tensor, rows: int, n: int, k: int,
                        up_tables: Mxfp4Tables | None = None, out: torch.Tensor | None = None,
-                       out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+                       out_dtype: torch.dtype = torch.bfloat16, workspace: torch.Tensor | None = None,
+                       splits: int = 0) -> torch.Tensor:
     """Per-expert W4A8 GEMM over expert-sorted rows (pli_gemm_grouped_mxfp4): out[r] = x_scale[t] decode(x8[t])
     W_e^T, t = gather[r] (None: r), for r in expert e's range of ``offsets``, W_e the expert's MXFP4 weight of
     ``tables``; with ``up_tables`` silu(. W1_e^T) * (. W3_e^T), SiLU and product in fp32, one rounding.  x8 [tokens,
     k] / x_scale as quantize_rows_fp8 writes them.  ``rows`` is the host bound rows_bound >= offsets[experts], the
     number of sorted rows (tokens * top_k after moe_route); ``out``, if given, holds that many rows of ``out_dtype``.
-    ``gather`` (or, without it, x8) holds offsets[experts] rows: a device value, so it is the caller's contract."""
+    ``gather`` (or, without it, x8) holds offsets[experts] rows: a device value, so it is the caller's contract.
+    ``workspace`` (bytes from gemm_grouped_mxfp4_workspace_bytes) lets a call of at most 32 rows split every expert's
+    K over workgroups (pli_gemm_grouped_mxfp4_ws; ``splits`` as there); None is the plain call."""
     if not x8.is_cuda:
         raise PliError("HIP path called with a CPU tensor")
     dev = x8.device
@@ -1768,12 +1781,16 @@ def gemm_grouped_mxfp4(x8: torch.Tensor, x_scale: torch.Tensor | None, gather: t
         raise PliError(f"gemm_grouped_mxfp4: out must be a {out_dtype} [>= {rows}, {n}] tensor on {dev} with a unit "
                        "column stride")
     up = (None, None) if up_tables is None else (up_tables.codes, up_tables.exps)
+    head = (_ptr(x8), _ptr(x_scale), _ptr(gather), _ptr(tables.codes), _ptr(tables.exps), _ptr(up[0]), _ptr(up[1]),
+            _ptr(out), _ptr(offsets), E, int(rows), int(n), int(k), _ldw(x8), tables.ldw, tables.lds,
+            max(out.stride(0), n), DTYPE_CODE[out_dtype])
     with _on_device(dev):
-        rc = lib().pli_gemm_grouped_mxfp4(_ptr(x8), _ptr(x_scale), _ptr(gather), _ptr(tables.codes), _ptr(tables.exps),
-                                          _ptr(up[0]), _ptr(up[1]), _ptr(out), _ptr(offsets), E, int(rows), int(n),
-                                          int(k), _ldw(x8), tables.ldw, tables.lds, max(out.stride(0), n),
-                                          DTYPE_CODE[out_dtype], _stream(dev))
-    _check(rc, "pli_gemm_grouped_mxfp4")
+        if workspace is None:
+            rc = lib().pli_gemm_grouped_mxfp4(*head, _stream(dev))
+        else:
+            rc = lib().pli_gemm_grouped_mxfp4_ws(*head, *_fp8w_workspace("gemm_grouped_mxfp4", workspace, dev),
+                                                 int(splits), _stream(dev))
+    _check(rc, "pli_gemm_grouped_mxfp4" if workspace is None else "pli_gemm_grouped_mxfp4_ws")
     return out
 
 

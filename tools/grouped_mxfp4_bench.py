@@ -11,6 +11,11 @@ token count, legs:
   mx_w13_gemm / mx_w2_gemm   gemm_grouped_mxfp4 alone on rows quantised beforehand
   quant_x / quant_h     quantize_rows_fp8 alone
   bf16_layer / mx_layer the whole layers (router, route, both grouped GEMMs, combine)
+and, up to 32 sorted rows (16 tokens), the split-K decode route (pli_gemm_grouped_mxfp4_ws) beside the plain call:
+  ws_w13 / ws_w2, ws_w13_gemm / ws_w2_gemm   the mx_* legs with a workspace (``--splits``: 0 lets the rule choose)
+  ws_layer              Mxfp4MoELayer.from_layer(split_decode=True)
+with the ratios mx / ws (> 1: the split route is faster than the plain call), bf16 / ws, and for the two ws_*_gemm
+legs the GB/s of MXFP4 bytes of the experts that have rows (codes and scale bytes of W1 + W3, or of W2).
 
 Protocol: tools/fp8w_linear_bench.py's (its helpers are imported).  At one token only two experts are read: 62 MB
 (W2) / 125 MB (W1, W3) of MXFP4 and 235 / 470 MB of bf16, not all past the 256 MiB Infinity Cache.  So every weight
@@ -46,6 +51,9 @@ from ch09 import MoEConfig, MoELayer, Mxfp4MoELayer  # noqa: E402
 DT, DEV = torch.bfloat16, "cuda"
 PAIRS = (("bf16_w13", "mx_w13"), ("bf16_w13", "mx_w13_gemm"), ("bf16_w2", "mx_w2"), ("bf16_w2", "mx_w2_gemm"),
          ("bf16_layer", "mx_layer"))
+WS_PAIRS = tuple((f"{side}_{leg}", f"ws_{leg}") for leg in ("w13", "w13_gemm", "w2", "w2_gemm", "layer")
+                 for side in ("mx", "bf16") if not (side == "bf16" and leg.endswith("_gemm")))
+WS_ROWS = Mxfp4MoELayer.SPLIT_ROWS
 
 
 def main() -> int:
@@ -57,6 +65,7 @@ def main() -> int:
     ap.add_argument("--layer-calls", type=int, default=20, help="eager layer calls per timed window")
     ap.add_argument("--bf16-copies", type=int, default=2, help="copies of the bf16 layer a leg walks in turn")
     ap.add_argument("--mx-copies", type=int, default=4, help="copies of the MXFP4 layer a leg walks in turn")
+    ap.add_argument("--splits", type=int, default=0, help="S of the ws_* legs (0: the rule chooses)")
     ap.add_argument("--out", help="also append the JSON lines to this file")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -70,6 +79,9 @@ def main() -> int:
         layers = [layer] + [copy.deepcopy(layer) for _ in range(a.bf16_copies - 1)]
         mxs = [Mxfp4MoELayer.from_layer(layer)]
         mxs += [copy.deepcopy(mxs[0]) for _ in range(a.mx_copies - 1)]
+        wss = [copy.copy(m) for m in mxs]  # the same weights and tables, the option on
+        for m in wss:
+            m.split_decode = True
     mx, bt, mt = mxs[0], [m._weight_tables() for m in layers], [m._weight_tables() for m in mxs]
     head = {"tool": "grouped_mxfp4_bench", "device": torch.cuda.get_device_name(0), "dtype": "bf16", "hidden": H,
             "expert_dim": I, "experts": cfg.num_experts, "top_k": k, "repeats": a.repeats, "window_s": a.window,
@@ -99,10 +111,20 @@ def main() -> int:
                 "mx_w2": [lambda t=t: g2(t, *q(h16)) for t in mt], "mx_w2_gemm": [lambda t=t: g2(t, h8, hs) for t in mt],
                 "quant_x": [lambda: q(xf)], "quant_h": [lambda: q(h16)],
             }
+            if rows <= WS_ROWS:
+                need = max(pli_hip.gemm_grouped_mxfp4_workspace_bytes(cfg.num_experts, rows, I, H, True, a.splits),
+                           pli_hip.gemm_grouped_mxfp4_workspace_bytes(cfg.num_experts, rows, H, I, False, a.splits))
+                work = torch.empty(max(need, 16), dtype=torch.uint8, device=DEV)
+                w13 = lambda t, c8, s: pli_hip.gemm_grouped_mxfp4(c8, s, gather, t[0], offsets, rows, I, H, up_tables=t[1], out=hm,  # noqa: E731
+                                                                  workspace=work, splits=a.splits)
+                w2 = lambda t, c8, s: pli_hip.gemm_grouped_mxfp4(c8, s, None, t[2], offsets, rows, H, I, out=ym, workspace=work,  # noqa: E731
+                                                                 splits=a.splits)
+                legs.update({"ws_w13": [lambda t=t: w13(t, *q(xf)) for t in mt], "ws_w13_gemm": [lambda t=t: w13(t, x8, xs) for t in mt],
+                             "ws_w2": [lambda t=t: w2(t, *q(h16)) for t in mt], "ws_w2_gemm": [lambda t=t: w2(t, h8, hs) for t in mt]})
             routes, times = fb.time_legs(a, legs)
             # the whole layers run eagerly (the router's launch clears its counters with a memset, which stays out of
             # captured graphs here): --layer-calls calls per window between two device events, alternating
-            models = {"bf16_layer": layers, "mx_layer": mxs}
+            models = {"bf16_layer": layers, "mx_layer": mxs, **({"ws_layer": wss} if rows <= WS_ROWS else {})}
             for leg, mdls in models.items():
                 for mdl in mdls:
                     mdl(x)
@@ -125,7 +147,16 @@ def main() -> int:
                 ratio = res[num]["us"] / res[den]["us"]
                 rec[f"{num}_over_{den}"] = round(ratio, 3)
                 rec[f"verdict_{den}"] = fb.verdict_of(ratio, max(res[num]["spread"], res[den]["spread"]), den)
-            line = json.dumps({**head, "tokens": T, "rows": rows, "routes": routes, **res, **rec,
+            if rows <= WS_ROWS:
+                for num, den in WS_PAIRS:
+                    ratio = res[num]["us"] / res[den]["us"]
+                    rec[f"{num}_over_{den}"] = round(ratio, 3)
+                    rec[f"verdict_{den}_vs_{num.split('_')[0]}"] = fb.verdict_of(ratio, max(res[num]["spread"], res[den]["spread"]), den)
+                active = int((offsets[1:] != offsets[:-1]).sum())  # experts that have rows: the bytes a call must stream
+                for leg, per_expert in (("ws_w13_gemm", 2 * I * (H // 2 + H // 32)), ("ws_w2_gemm", H * (I // 2 + I // 32))):
+                    res[leg]["mxfp4_mb"] = round(active * per_expert / 1e6, 1)
+                    res[leg]["mxfp4_gbps"] = round(active * per_expert / res[leg]["us"] / 1e3, 1)
+            line = json.dumps({**head, "tokens": T, "rows": rows, "splits": a.splits, "routes": routes, **res, **rec,
                                "format_error": fb.quant_error(mx(x), layer(x))})
         print(line, flush=True)
         if out:
