@@ -931,6 +931,88 @@ int pli_gemm_mxfp4(const void* x8, const float* x_scale, const void* w4,
                    int k, int64_t ldx8, int64_t ldw, int64_t lds, int64_t ldc,
                    int dtype, void* stream);
 
+/* MXFP4 activations (W4A4): a row quantiser that writes MXFP4 activations and
+ * an NT GEMM whose both operands are MXFP4, on
+ * v_mfma_scale_f32_32x32x64_f8f6f4 with two e2m1 operands (cbsz = blgp = 4:
+ * half the passes of any form with an 8-bit operand) and both hardware E8M0
+ * block scales live.  For prefill and batches of some hundred rows and more;
+ * nothing is widened and there is no workspace.  pli_gemm_mxfp4 is unchanged,
+ * a caller opts in by calling these functions.
+ *
+ * Activation format: x4 [m, k / 2] bytes of two e2m1 codes in the weight's
+ *   packing (element i in byte i / 2, even i in bits 3:0; ldx4 in bytes), x_exp
+ *   [m, k / 32] E8M0 bytes (leading dimension ldxs), x_scale device fp32 [m] or
+ *   NULL (all ones).  value[r, i] = decode_e2m1(code) * 2^(x_exp[r, i / 32] -
+ *   127) * x_scale[r].  The per-row factor is applied after the sum, as
+ *   pli_gemm_mxfp4 applies its x_scale; a producer of plain MXFP4 passes NULL.
+ * Scale contract of x_exp: x_exp - 127 in [-26, 26].  It is the largest
+ *   symmetric range [-R, R] for which, against a weight byte at either end of
+ *   the weight's contract (w_exp - 127 = -+96, unchanged), every non-zero term
+ *   code x code x 2^(e_w + e_x) is a normal fp32 number: the smallest term 0.5
+ *   * 0.5 * 2^(-96 - R) >= 2^-126 needs R <= 28, the largest 6 * 6 * 2^(96 + R)
+ *   = 1.125 * 2^(101 + R) < 2^128 needs R <= 26.  Inside both contracts the
+ *   terms lie in [2^-124, 36 * 2^122] with at most 4 significant bits.  Outside
+ *   a contract the outputs of that row of C (x_exp) or column (w_exp) are
+ *   unspecified, but no access leaves an operand.
+ *
+ * pli_quantize_rows_mxfp4: x [m, k] bf16 / fp16 (ldx in elements), k % 32 == 0
+ *   -> x4, x_exp, x_scale, all written by the call.  Per row: E_r =
+ *   floor(log2(amax_row)) - 2 over the finite elements, 0 for a row without a
+ *   finite non-zero element; x_scale[r] = 2^E_r (a power of two, subnormal
+ *   below 2^-126).  Per block of 32: e_b = floor(log2(amax_block)) - 2 - E_r,
+ *   clamped from below at -26 and never positive; x_exp = 127 + e_b, 127 for an
+ *   all-zero block; code = e2m1 round-to-nearest-even of clamp(x / 2^(E_r +
+ *   e_b), -6, 6), the rounding of the Python quantize_weight_mxfp4 (ties to the
+ *   even code, the sign of a zero kept).  Every step is exact arithmetic, so
+ *   the device is bitwise the Python quantize_rows_mxfp4 on a CPU tensor.
+ *   +-inf gives the code of +-6 and enters neither amax.  A NaN element gets
+ *   code 0, enters neither amax and sets its block's byte to 0xFF (e2m1 has no
+ *   NaN code): the GEMM then makes that row of C NaN.
+ *   Kernel "quant_rows_mxfp4", one workgroup per row.  With ldx % 8 == 0, ldx4
+ *   and ldxs % 4 == 0, x 16-byte and x4 / x_exp 4-byte aligned a row of up to
+ *   8192 elements is read once (held in registers between the row amax and
+ *   the encode) and the rest of a longer one twice; any other call reads x
+ *   twice.  k == 0 writes scale 1.0 and nothing else; m == 0 does nothing.
+ * pli_gemm_mxfp4_a4: C[r, j] = round_T( x_scale[r] * sum_i decode_e2m1(x4[r,
+ *   i]) * 2^(x_exp[r, i / 32] - 127) * decode_e2m1(w4[j, i]) * 2^(w_exp[j, i /
+ *   32] - 127)  (+ bias[j]) ).  w4, w_exp, ldw, lds are pli_gemm_mxfp4's; T
+ *   (dtype) is bf16 or fp16 and is the type of C (ldc in elements) and bias.
+ *   The sum is fp32; x_scale and the bias come after the sum; one rounding.
+ *   Codes and scales are read on the device: a captured call replays while they
+ *   change in place.  Nothing is allocated or synchronised.
+ * NaN: a 0xFF byte in w_exp makes exactly the outputs of its column j NaN, one
+ *   in x_exp exactly its row r, on every route.
+ * Routes, in this order, from host arguments only (csrc/mxfp4x_plan.h;
+ *   pli_last_route names the kernel):
+ *   1. m == 0 or n == 0: nothing, and the operands may be NULL; k == 0:
+ *      C = bias or 0 ("gemm_mxfp4_a4_generic").
+ *   2. "gemm_mxfp4_a4_mx": m >= 17, k % 256 == 0, x4 / w4 16-byte aligned,
+ *      ldx4 and ldw % 16 == 0, x_exp / w_exp 4-byte aligned and ldxs / lds % 4
+ *      == 0 (a lane loads the eight scale bytes of a K-step as two dwords), n
+ *      and ldc % 4 == 0, c 8-byte aligned.  gemm_fp8_mx's 128 x 128 tile at a
+ *      K-step of 256 codes: both operand images are 128 bytes per row, two 32
+ *      KiB LDS stages, 16 scaled MFMAs per wave and step, every operand one
+ *      ds_read_b128; ragged m / n edges by clamped loads and masked stores.
+ *      The order in which the instruction sums its 64 terms is its own, so this
+ *      route agrees with route 3 to fp32 rounding, and bitwise wherever every
+ *      partial sum is exact.
+ *   3. "gemm_mxfp4_a4_generic": one thread per output, fp32 fma in k order,
+ *      any shape, leading dimension and alignment.
+ * PLI_EINVAL before any HIP call, in this order: a dtype other than fp16 /
+ *   bf16, a negative shape, k % 32 != 0, a leading dimension below its width
+ *   (ldx >= k; ldx4, ldw >= k / 2; ldxs, lds >= k / 32; ldc >= n), a NULL
+ *   operand of a non-empty call (x_scale of the quantiser and both scale-byte
+ *   operands included; the GEMM's x_scale and bias may be NULL), a grid too
+ *   large. */
+int pli_quantize_rows_mxfp4(const void* x, int64_t ldx, void* x4, int64_t ldx4,
+                            void* x_exp, int64_t ldxs, float* x_scale, int m,
+                            int k, int dtype, void* stream);
+int pli_gemm_mxfp4_a4(const void* x4, const void* x_exp, const float* x_scale,
+                      const void* w4, const void* w_exp, const void* bias,
+                      void* c, int m, int n, int k, int64_t ldx4, int64_t ldxs,
+                      int64_t ldw, int64_t lds, int64_t ldc, int dtype,
+                      void* stream);
+
 /* Few rows over fp8 or MXFP4 weights: pli_gemm_fp8 / pli_gemm_mxfp4 with a
  * caller-owned device workspace, for calls of 17 .. 256 rows.  Such a call is
  * one or two rows of 128 x 128 tiles, far fewer workgroups than the device has

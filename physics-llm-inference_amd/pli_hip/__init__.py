@@ -132,6 +132,9 @@ _SIGS = {
     "pli_gemm_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_int, _vp],
     "pli_gemm_mxfp4": [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int,
                        _vp],
+    # MXFP4 activations (W4A4): the row quantiser and the all-FP4 NT GEMM
+    "pli_quantize_rows_mxfp4": [_vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp, _c_int, _c_int, _c_int, _vp],
+    "pli_gemm_mxfp4_a4": [_vp] * 7 + [_c_int] * 3 + [_c_i64] * 5 + [_c_int, _vp],
     "pli_gemm_grouped_mxfp4": [_vp] * 9 + [_c_int] * 4 + [_c_i64] * 4 + [_c_int, _vp],
     "pli_gemm_grouped_mxfp4_workspace_size": [_c_int] * 6,
     "pli_gemm_grouped_mxfp4_ws": [_vp] * 9 + [_c_int] * 4 + [_c_i64] * 4 + [_c_int, _vp, ctypes.c_size_t, _c_int, _vp],
@@ -1688,6 +1691,146 @@ def linear_mxfp4a(x: torch.Tensor, codes: torch.Tensor, exps: torch.Tensor, bias
     x8, x_scale = quantize_rows_fp8(x)
     return gemm_mxfp4(x8, x_scale, codes, exps, bias=bias, out=out, out_dtype=x.dtype, workspace=workspace,
                       splits=splits)
+
+
+# ------------------------------------------------- MXFP4 activations x MXFP4 weights (W4A4)
+# the scale contract of x_exp (include/pli.h, csrc/mxfp4x_plan.h kMxfp4xExpLo / Hi): x_exp - 127 of every byte
+MXFP4X_EXP_RANGE = (-26, 26)
+
+
+def _quantize_rows_mxfp4_torch(x: torch.Tensor):
+    """the rule of pli_quantize_rows_mxfp4 in torch ops (frexp / ldexp / round as in quantize_weight_mxfp4; float64
+    carries 2^-(E_r + e_b) over the whole bf16 range, every step exact)"""
+    xf = x.detach().double()
+    m, k = xf.shape
+    nan = torch.isnan(xf)
+    a = torch.where(torch.isfinite(xf), xf.abs(), torch.zeros_like(xf))
+    blk = a.reshape(m, k // MXFP4_BLOCK, MXFP4_BLOCK)
+    bmax = blk.amax(dim=2)
+    rmax = a.amax(dim=1) if k else torch.zeros(m, dtype=torch.float64)
+    zero = torch.zeros((), dtype=torch.int32)
+    # amax = f * 2^x with f in [0.5, 1): floor(log2(amax)) = x - 1, exactly
+    row_exp = torch.where(rmax > 0, torch.frexp(rmax)[1] - 3, zero)
+    blk_exp = torch.where(bmax > 0, (torch.frexp(bmax)[1] - 3 - row_exp[:, None]).clamp(min=MXFP4X_EXP_RANGE[0]), zero)
+    y = torch.where(nan, torch.zeros_like(xf), xf).reshape(m, -1, MXFP4_BLOCK)
+    y = torch.ldexp(y, -(row_exp[:, None] + blk_exp)[:, :, None]).clamp(-6.0, 6.0)
+    mag = y.abs()
+    mag = torch.where(mag < 2, torch.round(mag * 2), torch.where(mag < 4, torch.round(mag) + 2, torch.round(mag / 2) + 4))
+    code = (mag.to(torch.uint8) | (torch.signbit(y).to(torch.uint8) << 3)).reshape(m, k)
+    codes = (code[:, 0::2] | (code[:, 1::2] << 4)).contiguous()
+    exps = (blk_exp + 127).to(torch.uint8)
+    exps[nan.reshape(m, -1, MXFP4_BLOCK).any(dim=2)] = 0xFF
+    scale = torch.ldexp(torch.ones(m, dtype=torch.float64), row_exp).float()  # exact, subnormal below 2^-126
+    return codes, exps.contiguous(), scale.contiguous()
+
+
+def quantize_rows_mxfp4(x: torch.Tensor, out: tuple | None = None):
+    """MXFP4 quantisation of activations x [m, k] fp16 / bf16, k % 32 == 0: ``(codes, exps, scale)`` with codes uint8
+    [m, k / 2] (the weight's packing), exps uint8 [m, k / 32] (E8M0) and scale fp32 [m]; value = decode(code) *
+    2^(exps - 127) * scale[row].  Per row E_r = floor(log2(amax)) - 2 over the finite elements and scale = 2^E_r; per
+    block e_b = floor(log2(amax_block)) - 2 - E_r clamped from below at MXFP4X_EXP_RANGE[0], exps = 127 + e_b, codes
+    by the rounding of quantize_weight_mxfp4.  +-inf gives +-6; a NaN element gets code 0 and makes its block's byte
+    0xFF; neither enters an amax.  On a device tensor this is the quant_rows_mxfp4 kernel, on a CPU tensor torch ops,
+    bitwise the same.  ``out``: a (codes, exps, scale) triple to write into (device path; unit column strides)."""
+    if x.dim() != 2 or x.shape[1] % MXFP4_BLOCK:
+        raise PliError(f"quantize_rows_mxfp4 expects a 2-D x with k % 32 == 0, got {tuple(x.shape)}")
+    if x.dtype not in (torch.float16, torch.bfloat16):
+        raise PliError(f"quantize_rows_mxfp4: activations must be fp16 or bf16, got {x.dtype}")
+    if not x.is_cuda:
+        if out is not None:
+            raise PliError("quantize_rows_mxfp4: out is for the device path")
+        return _quantize_rows_mxfp4_torch(x)
+    dev = x.device
+    if x.numel() and x.stride(1) != 1:
+        x = x.contiguous()
+    m, k = x.shape
+    if out is None:
+        codes = torch.empty((m, k // 2), dtype=torch.uint8, device=dev)
+        exps = torch.empty((m, k // MXFP4_BLOCK), dtype=torch.uint8, device=dev)
+        scale = torch.empty((m,), dtype=torch.float32, device=dev)
+    else:
+        codes, exps, scale = out
+        for t, name, width in ((codes, "codes", k // 2), (exps, "exps", k // MXFP4_BLOCK)):
+            if (not t.is_cuda or t.device != dev or t.dtype != torch.uint8 or tuple(t.shape) != (m, width) or
+                    (t.numel() and t.stride(1) != 1)):
+                raise PliError(f"quantize_rows_mxfp4: out {name} must be uint8 [{m}, {width}] on {dev} with a unit "
+                               "column stride")
+        if (not scale.is_cuda or scale.device != dev or scale.dtype != torch.float32 or tuple(scale.shape) != (m,) or
+                not scale.is_contiguous()):
+            raise PliError(f"quantize_rows_mxfp4: out scale must be a contiguous fp32 [{m}] tensor on {dev}")
+    with _on_device(dev):
+        rc = lib().pli_quantize_rows_mxfp4(_ptr(x), max(x.stride(0), k) if m > 1 else k, _ptr(codes), _ldw(codes),
+                                           _ptr(exps), _ldw(exps), _ptr(scale), m, k, _dtype_code(x), _stream(dev))
+    _check(rc, "pli_quantize_rows_mxfp4")
+    return codes, exps, scale
+
+
+def gemm_mxfp4_a4(x4: torch.Tensor, x_exp: torch.Tensor, x_scale: torch.Tensor | None, codes: torch.Tensor,
+                  exps: torch.Tensor, bias: torch.Tensor | None = None, out: torch.Tensor | None = None,
+                  out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """C = (x_scale[:, None] * X) W^T (+ bias) with X = dequantize_weight_mxfp4(x4, x_exp) and W =
+    dequantize_weight_mxfp4(codes, exps): x4 uint8 [m, k / 2], x_exp uint8 [m, k / 32] and x_scale fp32 [m] or None
+    (ones) as quantize_rows_mxfp4 writes them, codes / exps as linear_mxfp4w takes them (any row stride, used in
+    place); C and bias ``out_dtype`` (bf16 / fp16).  fp32 sum, x_scale and bias after the sum, one rounding.  Scale
+    bytes: x_exp within MXFP4X_EXP_RANGE of 127, exps within MXFP4A_EXP_RANGE."""
+    what = "gemm_mxfp4_a4"
+    for t in (x4, x_exp):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise PliError("HIP path called with a CPU tensor")
+    dev = x4.device
+    if (x4.dim() != 2 or x_exp.dim() != 2 or x4.dtype != torch.uint8 or x_exp.dtype != torch.uint8 or
+            x_exp.device != dev or x4.shape[0] != x_exp.shape[0] or x4.shape[1] != 16 * x_exp.shape[1]):
+        raise PliError(f"{what}: x4 uint8 [m, k / 2] and x_exp uint8 [m, k / 32] on one device expected, got "
+                       f"{x4.dtype}{tuple(x4.shape)} {x_exp.dtype}{tuple(x_exp.shape)}")
+    m, k = x4.shape[0], 2 * x4.shape[1]
+    for t in (x4, x_exp):
+        if t.numel() and t.stride(1) != 1:
+            raise PliError(f"{what}: x4 and x_exp need a unit column stride (they are used in place)")
+    if x_scale is not None and (not x_scale.is_cuda or x_scale.device != dev or x_scale.dtype != torch.float32 or
+                                tuple(x_scale.shape) != (m,) or not x_scale.is_contiguous()):
+        raise PliError(f"{what}: x_scale must be None or a contiguous fp32 [{m}] tensor on {dev}")
+    for t, name, width in ((codes, "codes", k // 2), (exps, "exps", k // MXFP4_BLOCK)):
+        if not isinstance(t, torch.Tensor):
+            raise PliError(f"{what}: {name} must be a tensor, got {type(t).__name__} (the scale bytes have no default)")
+        if not t.is_cuda:
+            raise PliError("HIP path called with a CPU tensor")
+        if t.device != dev or t.dtype != torch.uint8:
+            raise PliError(f"{what}: {name} must be a torch.uint8 tensor on {dev}, got {t.dtype} on {t.device}")
+        if t.dim() != 2 or t.shape[0] != codes.shape[0] or t.shape[1] != width:
+            raise PliError(f"{what} shape mismatch: x4{tuple(x4.shape)} {name}{tuple(t.shape)}")
+        if t.numel() and t.stride(1) != 1:
+            raise PliError(f"{what}: {name} need a unit column stride (they are used in place)")
+    if out_dtype not in (torch.float16, torch.bfloat16):
+        raise PliError(f"{what}: out_dtype must be fp16 or bf16, got {out_dtype}")
+    n = codes.shape[0]
+    if bias is not None:
+        if not bias.is_cuda or bias.device != dev or bias.dtype != out_dtype or tuple(bias.shape) != (n,):
+            raise PliError(f"{what}: bias must be a {out_dtype} [{n}] tensor on {dev}")
+        bias = bias.contiguous()
+    if out is None:
+        out = torch.empty((m, n), dtype=out_dtype, device=dev)
+    else:
+        if out.dtype != out_dtype:
+            raise PliError(f"{what}: out is {out.dtype}, out_dtype {out_dtype}")
+        _check_out(out, out, (m, n), what)
+        if out.device != dev:
+            raise PliError(f"tensors on different devices: {out.device} vs {dev}")
+    with _on_device(dev):
+        rc = lib().pli_gemm_mxfp4_a4(_ptr(x4), _ptr(x_exp), _ptr(x_scale), _ptr(codes), _ptr(exps), _ptr(bias),
+                                     _ptr(out), m, n, k, _ldw(x4), _ldw(x_exp), _ldw(codes), _ldw(exps),
+                                     max(out.stride(0), n), DTYPE_CODE[out_dtype], _stream(dev))
+    _check(rc, "pli_gemm_mxfp4_a4")
+    return out
+
+
+def linear_mxfp4a4(x: torch.Tensor, codes: torch.Tensor, exps: torch.Tensor, bias: torch.Tensor | None = None,
+                   out: torch.Tensor | None = None) -> torch.Tensor:
+    """x W^T (+ bias) over MXFP4 weights with the activations in MXFP4 too: quantize_rows_mxfp4(x), then
+    gemm_mxfp4_a4 (the sibling of linear_mxfp4a); the result has x's dtype.  Bitwise the two calls."""
+    if not x.is_cuda:
+        raise PliError("HIP path called with a CPU tensor")
+    x4, x_exp, x_scale = quantize_rows_mxfp4(x)
+    return gemm_mxfp4_a4(x4, x_exp, x_scale, codes, exps, bias=bias, out=out, out_dtype=x.dtype)
 
 
 # ------------------------------------------------- MXFP4 expert weights (grouped W4A8)
