@@ -1122,6 +1122,72 @@ int pli_gemm_grouped_mxfp4(const void* x8, const float* x_scale,
                            int n, int k, int64_t ldx8, int64_t ldw, int64_t lds,
                            int64_t ldc, int dtype, void* stream);
 
+/* MXFP4 activations for the MoE layer: pli_gemm_grouped_mxfp4 with the
+ * activation operand of pli_gemm_mxfp4_a4 (W4A4), for prefill-sized expert
+ * batches (hundreds of rows per expert and more).
+ *
+ * Semantics: for every expert e and sorted row r in [offsets[e],
+ *   offsets[e + 1]), t = gather ? gather[r] : r:
+ *     c[r, j] = round_T( x_scale[t] * sum_i decode_e2m1(x4[t, i]) *
+ *               2^(x_exp[t, i / 32] - 127) * decode_e2m1(w4_e[j, i]) *
+ *               2^(w_exp_e[j, i / 32] - 127) ),
+ *   the sum in fp32, x_scale after the sum, one rounding; or, with the up
+ *   tables, g and u those two finished fp32 values, c[r, j] =
+ *   round_T(silu(g) * u): SiLU and the product in fp32, one rounding, the rule
+ *   of pli_gemm_grouped.
+ * Operands: x4 [tokens, k / 2], x_exp [tokens, k / 32] and x_scale [tokens]
+ *   exactly as pli_quantize_rows_mxfp4 writes them (x_scale NULL: ones); the
+ *   weight tables, offsets, gather, rows_bound and c exactly as
+ *   pli_gemm_grouped_mxfp4 takes them, nothing re-packed.  The scale contracts
+ *   are pli_gemm_mxfp4_a4's (w_exp - 127 in [-96, 96], x_exp - 127 in [-26,
+ *   26]).  NaN: a 0xFF byte in expert e's w_exp row j (or in its up matrix
+ *   alone) makes exactly column j of e's rows NaN, one in token t's x_exp
+ *   exactly the sorted rows that gather t, on every route.  No atomics, no
+ *   workspace, nothing allocated or synchronised; everything is read on the
+ *   device, so a captured call replays.
+ * Routes, from host arguments only (csrc/grouped_mxfp4x_plan.h; pli_last_route
+ *   names the kernel):
+ *   1. rows_bound == 0 or n == 0: nothing, and the operands may be NULL.
+ *   2. "gemm_grouped_mxfp4_a4": k % 256 == 0 (k > 0), n % 16 == 0, x4 16-byte
+ *      aligned, ldx4 and ldw % 16 == 0, x_exp 4-byte aligned, ldxs and lds % 4
+ *      == 0, ldc % 4 == 0, c 8-byte aligned, ceil(rows_bound / 128) + experts
+ *      <= 65535.  gemm_mxfp4_a4_mx's tile (128 weight rows x 128 sorted rows,
+ *      K-step of 256 codes, two LDS stages fed by LDS-DMA, every operand one
+ *      ds_read_b128, both sides' E8M0 bytes into the instruction) per (weight
+ *      tile, slot): the slot's (expert, slab) comes from a scan of offsets, the
+ *      activation rows and their scale bytes through gather.  With the up
+ *      tables a stage holds three images (96 KiB of LDS in all) and an
+ *      activation fragment is read once for both matrices.
+ *   3. "gemm_grouped_mxfp4_a4_generic": one thread per output element, fp32
+ *      fma in k order, any shape, leading dimension and alignment (k == 0:
+ *      zeros).
+ * PLI_EINVAL before any HIP call, in this order: a dtype other than fp16 /
+ *   bf16; experts < 1 or a negative shape; k % 32 != 0; a leading dimension
+ *   below its width (ldx4 >= k / 2, ldxs >= k / 32, ldw >= k / 2, lds >= k /
+ *   32, ldc >= n); then, for a non-empty call, a NULL c, offsets, x4, x_exp or
+ *   table (x_scale and gather may be NULL); one up table without the other; a
+ *   grid too large.
+ * Which call (tools/grouped_mxfp4_a4_bench.py, MI355X, H 4096, 8 experts x
+ *   14336, top-2, bf16, two runs in profiles/grouped_mxfp4_a4/): against
+ *   pli_gemm_grouped_mxfp4 on the same routing this call alone is 1.33-1.34x
+ *   (W1 / W3 SwiGLU) and 1.32x (W2) faster at 512 tokens, 1.37x and 1.39x at
+ *   2048, 1.36x and 1.38x at 8192; with the row quantisers 1.23-1.35x, the
+ *   whole layer 1.21x / 1.28x / 1.29x.  No measured token count loses; below
+ *   512 tokens nothing was measured, and at most 32 sorted rows are the
+ *   ground of pli_gemm_grouped_mxfp4_ws.  MXFP4 rows cost accuracy (the
+ *   layer's rms error against the bf16 layer: 0.330 of rms(y) against 0.245
+ *   with fp8 rows, N(0,1) weights), so the layer takes them only on request. */
+int pli_gemm_grouped_mxfp4_a4(const void* x4, const void* x_exp,
+                              const float* x_scale, const int32_t* gather,
+                              const void* const* w4_ptrs,
+                              const void* const* wexp_ptrs,
+                              const void* const* wu4_ptrs,
+                              const void* const* wuexp_ptrs, void* c,
+                              const int32_t* offsets, int experts,
+                              int rows_bound, int n, int k, int64_t ldx4,
+                              int64_t ldxs, int64_t ldw, int64_t lds,
+                              int64_t ldc, int dtype, void* stream);
+
 /* MoE decode over MXFP4 expert weights: pli_gemm_grouped_mxfp4 with a
  * caller-owned device workspace, for calls of at most 32 sorted rows (1 .. 16
  * tokens at top-2).  Such a call only streams the weights of the few experts

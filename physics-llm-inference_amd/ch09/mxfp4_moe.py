@@ -18,6 +18,12 @@ product in fp32, one rounding per stage.  ``MoELayer`` itself is unchanged.
 ``from_layer(..., split_decode=True)`` is for decode: with at most 32 sorted rows (16 tokens at top-2) both grouped
 calls get one cached workspace and run ``pli_gemm_grouped_mxfp4_ws``, which splits every expert's K over workgroups.
 Above 32 rows, on the CPU and with the option off (the default) nothing changes.
+
+``from_layer(..., activations="mxfp4")`` (W4A4, an explicit opt-in for prefill-sized batches) replaces steps 2-5 with
+``quantize_rows_mxfp4(x)`` -> ``pli_gemm_grouped_mxfp4_a4`` with the W1 / W3 tables -> ``quantize_rows_mxfp4(h)`` ->
+``pli_gemm_grouped_mxfp4_a4`` with the W2 tables; it needs hidden_dim and expert_dim to be multiples of 256, and the
+torch form runs the same arithmetic through ``_quantize_rows_mxfp4_torch``.  ``split_decode`` applies to the fp8 path
+only: with ``"mxfp4"`` a call of at most 32 rows runs the plain W4A4 kernel.  The default ``"fp8"`` is the path above.
 """
 from __future__ import annotations
 
@@ -42,16 +48,22 @@ class Mxfp4MoELayer(nn.Module):
         self._tables = None  # (pointer key, w1 tables, w3 tables, w2 tables)
         self.split_decode = False  # up to SPLIT_ROWS sorted rows: both grouped calls split K over a cached workspace
         self._workspace = None
+        self.activations = "fp8"  # "mxfp4": both grouped calls take MXFP4 rows (W4A4)
 
     SPLIT_ROWS = 32  # pli_gemm_grouped_mxfp4_ws's row bound
 
     @classmethod
-    def from_layer(cls, layer: MoELayer, dtype: torch.dtype = torch.bfloat16,
-                   split_decode: bool = False) -> "Mxfp4MoELayer":
+    def from_layer(cls, layer: MoELayer, dtype: torch.dtype = torch.bfloat16, split_decode: bool = False,
+                   activations: str = "fp8") -> "Mxfp4MoELayer":
+        """``activations``: "fp8" (W4A8, the default) or "mxfp4" (W4A4); ``split_decode`` applies to "fp8" only: with
+        "mxfp4" a call of at most SPLIT_ROWS rows runs the plain W4A4 kernel"""
+        if activations not in ("fp8", "mxfp4"):
+            raise ValueError(f"activations must be 'fp8' or 'mxfp4', got {activations!r}")
         q = lambda lin: pli_hip.quantize_weight_mxfp4(lin.weight, dtype)  # noqa: E731
         new = cls(layer.config, layer.router, [q(e.w1) for e in layer.experts], [q(e.w3) for e in layer.experts],
                   [q(e.w2) for e in layer.experts])
         new.split_decode = split_decode
+        new.activations = activations
         return new
 
     def _split_workspace(self, rows: int, device) -> torch.Tensor | None:
@@ -79,7 +91,8 @@ class Mxfp4MoELayer(nn.Module):
 
     def _grouped_ok(self, x: torch.Tensor) -> bool:
         c = self.config
-        return (x.dtype in (torch.bfloat16, torch.float16) and c.hidden_dim % 128 == 0 and c.expert_dim % 128 == 0
+        step = 256 if self.activations == "mxfp4" else 128  # the K-step of the grouped kernel's route
+        return (x.dtype in (torch.bfloat16, torch.float16) and c.hidden_dim % step == 0 and c.expert_dim % step == 0
                 and c.num_experts <= 64 and c.num_experts_per_tok <= 8 and c.num_experts % 8 == 0)
 
     def _forward_hip(self, x_flat: torch.Tensor) -> torch.Tensor:
@@ -89,6 +102,12 @@ class Mxfp4MoELayer(nn.Module):
         w, _, pos, gather, offsets = pli_hip.moe_route(logits, k, c.normalize_expert_weights)
         t1, t3, t2 = self._weight_tables()
         rows = T * k
+        if self.activations == "mxfp4":
+            h = pli_hip.gemm_grouped_mxfp4_a4(*pli_hip.quantize_rows_mxfp4(x_flat), gather, t1, offsets, rows,
+                                              c.expert_dim, c.hidden_dim, up_tables=t3, out_dtype=x_flat.dtype)
+            y = pli_hip.gemm_grouped_mxfp4_a4(*pli_hip.quantize_rows_mxfp4(h), None, t2, offsets, rows, c.hidden_dim,
+                                              c.expert_dim, out_dtype=x_flat.dtype)
+            return pli_hip.moe_combine(y, pos, w, T)
         ws = self._split_workspace(rows, x_flat.device)
         x8, xs = pli_hip.quantize_rows_fp8(x_flat)
         h = pli_hip.gemm_grouped_mxfp4(x8, xs, gather, t1, offsets, rows, c.expert_dim, c.hidden_dim, up_tables=t3,
@@ -117,7 +136,13 @@ class Mxfp4MoELayer(nn.Module):
         def lin(codes8, scale, pair):  # fp32 sum of the exact products, the row scale after it
             return (codes8.float() @ deq(*pair).t()) * scale[:, None]
 
-        x8, xs = pli_hip._quantize_rows_fp8_torch(x_flat)
+        if self.activations == "mxfp4":  # the rows' values with their block scales, the row scale kept apart
+            def quant(t):
+                codes, exps, scale = pli_hip._quantize_rows_mxfp4_torch(t)
+                return deq(codes, exps), scale
+        else:
+            quant = pli_hip._quantize_rows_fp8_torch
+        x8, xs = quant(x_flat)
         w1, w3, w2 = (self._weights(n) for n in ("w1", "w3", "w2"))
         out = torch.zeros(x_flat.shape, dtype=torch.float32, device=x_flat.device)
         for kk in range(c.num_experts_per_tok):  # pli_moe_combine's order: fp32 fma over the slots in turn
@@ -127,7 +152,7 @@ class Mxfp4MoELayer(nn.Module):
                 if rows.numel() == 0:
                     continue
                 g, u = lin(x8[rows], xs[rows], w1[e]), lin(x8[rows], xs[rows], w3[e])
-                h8, hs = pli_hip._quantize_rows_fp8_torch((g / (1 + torch.exp(-g)) * u).to(dt))
+                h8, hs = quant((g / (1 + torch.exp(-g)) * u).to(dt))
                 y[rows] = lin(h8, hs, w2[e]).to(dt).float()
                 if trace is not None:
                     trace.append((rows, weights[rows, kk], h8.float() * hs[:, None], deq(*w2[e]), y[rows]))
@@ -150,6 +175,8 @@ if __name__ == "__main__":
     x = torch.randn(2, 16, 256).bfloat16()
     if torch.cuda.is_available():
         moe, x = moe.cuda(), x.cuda()
-    q = Mxfp4MoELayer.from_layer(moe)
-    y, yq = moe(x).float(), q(x).float()
-    print(f"bf16 layer vs MXFP4 experts: rms {float((y - yq).pow(2).mean().sqrt()):.4f} of {float(y.pow(2).mean().sqrt()):.4f}")
+    y = moe(x).float()
+    for act in ("fp8", "mxfp4"):
+        yq = Mxfp4MoELayer.from_layer(moe, activations=act)(x).float()
+        print(f"bf16 layer vs MXFP4 experts, {act} rows: rms {float((y - yq).pow(2).mean().sqrt()):.4f} of "
+              f"{float(y.pow(2).mean().sqrt()):.4f}")

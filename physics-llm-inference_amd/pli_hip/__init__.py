@@ -136,6 +136,7 @@ _SIGS = {
     "pli_quantize_rows_mxfp4": [_vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp, _c_int, _c_int, _c_int, _vp],
     "pli_gemm_mxfp4_a4": [_vp] * 7 + [_c_int] * 3 + [_c_i64] * 5 + [_c_int, _vp],
     "pli_gemm_grouped_mxfp4": [_vp] * 9 + [_c_int] * 4 + [_c_i64] * 4 + [_c_int, _vp],
+    "pli_gemm_grouped_mxfp4_a4": [_vp] * 10 + [_c_int] * 4 + [_c_i64] * 5 + [_c_int, _vp],
     "pli_gemm_grouped_mxfp4_workspace_size": [_c_int] * 6,
     "pli_gemm_grouped_mxfp4_ws": [_vp] * 9 + [_c_int] * 4 + [_c_i64] * 4 + [_c_int, _vp, ctypes.c_size_t, _c_int, _vp],
     # the split-K forms for 17 .. 256 rows: the plain signatures plus workspace, workspace_bytes, splits before the stream
@@ -1881,6 +1882,33 @@ def gemm_grouped_mxfp4_workspace_bytes(experts: int, rows: int, n: int, k: int, 
                                                            int(splits)))
 
 
+def _check_grouped_mxfp4(what: str, xname: str, x: torch.Tensor, xk: int, gather, tables, up_tables, offsets,
+                         rows: int, n: int, k: int, out, out_dtype):
+    """the table, shape (a row of the codes ``x`` holds ``xk`` elements of k), routing and output checks the grouped
+    MXFP4 calls share; returns (experts, out)"""
+    dev = x.device
+    E = offsets.numel() - 1
+    if E < 1:
+        raise PliError(f"{what}: offsets needs experts + 1 >= 2 entries")
+    for t in (tables, up_tables):
+        if t is not None and (len(t.weights) != E or (t.n, t.k) != (n, k) or t.codes.device != dev or
+                              (t.ldw, t.lds) != (tables.ldw, tables.lds)):
+            raise PliError(f"{what}: tables of {len(t.weights)} experts [{t.n}, {t.k}] do not match "
+                           f"{E} experts [{n}, {k}] on {dev}")
+    if xk != k:
+        raise PliError(f"{what} shape mismatch: {xname}{tuple(x.shape)} k={k}")
+    for t, name in ((gather, "gather"), (offsets, "offsets")):
+        if t is not None and (t.device != dev or t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous()):
+            raise PliError(f"{what}: {name} must be a contiguous 1-D int32 tensor on {dev}")
+    if out is None:
+        out = torch.empty(max(rows, 1), n, device=dev, dtype=out_dtype)
+    elif (out.dtype != out_dtype or out.device != dev or out.dim() != 2 or out.shape[0] < rows or out.shape[1] != n or
+          (out.numel() and out.stride(1) != 1)):
+        raise PliError(f"{what}: out must be a {out_dtype} [>= {rows}, {n}] tensor on {dev} with a unit "
+                       "column stride")
+    return E, out
+
+
 def gemm_grouped_mxfp4(x8: torch.Tensor, x_scale: torch.Tensor | None, gather: torch.Tensor | None,
                        tables: Mxfp4Tables, offsets: torch.Tensor, rows: int, n: int, k: int,
                        up_tables: Mxfp4Tables | None = None, out: torch.Tensor | None = None,
@@ -1904,25 +1932,8 @@ def gemm_grouped_mxfp4(x8: torch.Tensor, x_scale: torch.Tensor | None, gather: t
     if x_scale is not None and (x_scale.device != dev or x_scale.dtype != torch.float32 or
                                 tuple(x_scale.shape) != (x8.shape[0],) or not x_scale.is_contiguous()):
         raise PliError(f"gemm_grouped_mxfp4: x_scale must be None or a contiguous fp32 [{x8.shape[0]}] tensor on {dev}")
-    E = offsets.numel() - 1
-    if E < 1:
-        raise PliError("gemm_grouped_mxfp4: offsets needs experts + 1 >= 2 entries")
-    for t in (tables, up_tables):
-        if t is not None and (len(t.weights) != E or (t.n, t.k) != (n, k) or t.codes.device != dev or
-                              (t.ldw, t.lds) != (tables.ldw, tables.lds)):
-            raise PliError(f"gemm_grouped_mxfp4: tables of {len(t.weights)} experts [{t.n}, {t.k}] do not match "
-                           f"{E} experts [{n}, {k}] on {dev}")
-    if x8.shape[1] != k:
-        raise PliError(f"gemm_grouped_mxfp4 shape mismatch: x8{tuple(x8.shape)} k={k}")
-    for t, name in ((gather, "gather"), (offsets, "offsets")):
-        if t is not None and (t.device != dev or t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous()):
-            raise PliError(f"gemm_grouped_mxfp4: {name} must be a contiguous 1-D int32 tensor on {dev}")
-    if out is None:
-        out = torch.empty(max(rows, 1), n, device=dev, dtype=out_dtype)
-    elif (out.dtype != out_dtype or out.device != dev or out.dim() != 2 or out.shape[0] < rows or out.shape[1] != n or
-          (out.numel() and out.stride(1) != 1)):
-        raise PliError(f"gemm_grouped_mxfp4: out must be a {out_dtype} [>= {rows}, {n}] tensor on {dev} with a unit "
-                       "column stride")
+    E, out = _check_grouped_mxfp4("gemm_grouped_mxfp4", "x8", x8, x8.shape[1], gather, tables, up_tables, offsets, rows,
+                                  n, k, out, out_dtype)
     up = (None, None) if up_tables is None else (up_tables.codes, up_tables.exps)
     head = (_ptr(x8), _ptr(x_scale), _ptr(gather), _ptr(tables.codes), _ptr(tables.exps), _ptr(up[0]), _ptr(up[1]),
             _ptr(out), _ptr(offsets), E, int(rows), int(n), int(k), _ldw(x8), tables.ldw, tables.lds,
@@ -1934,6 +1945,44 @@ def gemm_grouped_mxfp4(x8: torch.Tensor, x_scale: torch.Tensor | None, gather: t
             rc = lib().pli_gemm_grouped_mxfp4_ws(*head, *_fp8w_workspace("gemm_grouped_mxfp4", workspace, dev),
                                                  int(splits), _stream(dev))
     _check(rc, "pli_gemm_grouped_mxfp4" if workspace is None else "pli_gemm_grouped_mxfp4_ws")
+    return out
+
+
+def gemm_grouped_mxfp4_a4(x4: torch.Tensor, x_exp: torch.Tensor, x_scale: torch.Tensor | None,
+                          gather: torch.Tensor | None, tables: Mxfp4Tables, offsets: torch.Tensor, rows: int, n: int,
+                          k: int, up_tables: Mxfp4Tables | None = None, out: torch.Tensor | None = None,
+                          out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """Per-expert W4A4 GEMM over expert-sorted rows (pli_gemm_grouped_mxfp4_a4): gemm_grouped_mxfp4 with the
+    activation operand of gemm_mxfp4_a4.  x4 uint8 [tokens, k / 2], x_exp uint8 [tokens, k / 32] and x_scale fp32
+    [tokens] or None (ones) as quantize_rows_mxfp4 writes them (unit column strides, used in place); ``gather``,
+    ``tables``, ``offsets``, ``rows``, ``up_tables`` and ``out`` as gemm_grouped_mxfp4 takes them.  fp32 sum, x_scale
+    after the sum, SiLU and product in fp32, one rounding.  Scale bytes: x_exp within MXFP4X_EXP_RANGE of 127."""
+    what = "gemm_grouped_mxfp4_a4"
+    for t in (x4, x_exp):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise PliError("HIP path called with a CPU tensor")
+    dev = x4.device
+    if (x4.dim() != 2 or x_exp.dim() != 2 or x4.dtype != torch.uint8 or x_exp.dtype != torch.uint8 or
+            x_exp.device != dev or x4.shape[0] != x_exp.shape[0] or x4.shape[1] != 16 * x_exp.shape[1]):
+        raise PliError(f"{what}: x4 uint8 [tokens, k / 2] and x_exp uint8 [tokens, k / 32] on one device expected, got "
+                       f"{x4.dtype}{tuple(x4.shape)} {x_exp.dtype}{tuple(x_exp.shape)}")
+    for t in (x4, x_exp):
+        if t.numel() and t.stride(1) != 1:
+            raise PliError(f"{what}: x4 and x_exp need a unit column stride (they are used in place)")
+    if out_dtype not in (torch.float16, torch.bfloat16):
+        raise PliError(f"{what}: out_dtype must be fp16 or bf16, got {out_dtype}")
+    if x_scale is not None and (x_scale.device != dev or x_scale.dtype != torch.float32 or
+                                tuple(x_scale.shape) != (x4.shape[0],) or not x_scale.is_contiguous()):
+        raise PliError(f"{what}: x_scale must be None or a contiguous fp32 [{x4.shape[0]}] tensor on {dev}")
+    E, out = _check_grouped_mxfp4(what, "x4", x4, 2 * x4.shape[1], gather, tables, up_tables, offsets, rows, n, k, out,
+                                  out_dtype)
+    up = (None, None) if up_tables is None else (up_tables.codes, up_tables.exps)
+    with _on_device(dev):
+        rc = lib().pli_gemm_grouped_mxfp4_a4(_ptr(x4), _ptr(x_exp), _ptr(x_scale), _ptr(gather), _ptr(tables.codes),
+                                             _ptr(tables.exps), _ptr(up[0]), _ptr(up[1]), _ptr(out), _ptr(offsets), E,
+                                             int(rows), int(n), int(k), _ldw(x4), _ldw(x_exp), tables.ldw, tables.lds,
+                                             max(out.stride(0), n), DTYPE_CODE[out_dtype], _stream(dev))
+    _check(rc, "pli_gemm_grouped_mxfp4_a4")
     return out
 
 
