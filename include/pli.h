@@ -559,6 +559,106 @@ int pli_kv_append_varlen_paged_fp8(const void* k_new, const void* v_new,
                                    const int64_t* strides, int dtype,
                                    void* stream);
 
+/* Decode attention and the appends over an MXFP4 KV pool (OCP Microscaling
+ * FP4): 4.25 bits per element, head_dim / 2 + head_dim / 32 bytes per (token,
+ * kv head) -- 68 at head_dim 128 against 128 for the fp8 pool and 256 for a
+ * 16-bit one, so the same memory holds 1.88x the tokens of the fp8 cache.
+ * Packed (varlen) attention over such a pool is not provided.
+ *
+ * Code pools: k_pool / v_pool are byte pools in the paged layout above,
+ *   head_dim / 2 bytes per (token, kv head): element i of a row lives in byte
+ *   i / 2, even i in bits 3:0, odd i in bits 7:4 (pli_linear_mxfp4w's packing).
+ *   Their strides (strides[3..8]) are in bytes.
+ * Scale pools: k_exp_pool / v_exp_pool are byte pools of their own with their
+ *   own {page, token, head} strides in bytes, exp_strides[6] = {k_page,
+ *   k_token, k_head, v_page, v_token, v_head}.  A (token, kv head) has
+ *   head_dim / 32 contiguous E8M0 bytes, byte b covering elements [32 b, 32 b +
+ *   32).  They are never NULL on a non-empty call.
+ * Value: decode_e2m1(code) * 2^(exp - 127) (csrc/fp4_codec.h).  There are no
+ *   per-head fp32 scales: the block scales carry the range.
+ * Shapes: head_dim % 32 == 0 in every call.
+ * Read contract: pli_gemv_mxfp4w's, by q's type: exp - 127 in [-125, 125] for
+ *   bf16 and fp32 q, in [-13, 13] for fp16 q.  Inside it the widening to q's
+ *   type with the block scale folded in is exact, so the result is attention
+ *   over the dequantised pool with the arithmetic of the 16-bit kernels
+ *   (bitwise pli_attn_decode_paged over a pool of the dequantised values on the
+ *   MFMA route).  Outside it the outputs of the query rows that see the key are
+ *   unspecified; no access leaves an operand.
+ * NaN: a 0xFF scale byte in a K or V row among a sequence's first n_kv tokens
+ *   makes every element of every query row of that sequence that sees the key
+ *   NaN; other sequences are untouched bit for bit.  Tokens at or past n_kv and
+ *   pages no table row names are never read (the clamped-address rule of the
+ *   paged kernels, for both pools).
+ * Append (the write rule), per block of 32 source elements, whatever the
+ *   source type: e = clamp(floor(log2(amax over the finite elements)) - 2, -13,
+ *   13), 0 for an all-zero block, so one pool serves bf16 and fp16 queries; the
+ *   byte is e + 127; each code is the e2m1 round-to-nearest-even of clamp(x /
+ *   2^e, -6, 6), ties to the even code, the sign of zero kept.  +-inf gets the
+ *   code of +-6 and does not enter amax; a NaN element gets code 0, does not
+ *   enter amax and sets its block's byte to 0xFF (pli_quantize_rows_mxfp4's
+ *   rules).  For finite input this is bit for bit the Python
+ *   quantize_weight_mxfp4(rows.reshape(-1, D), torch.float16).
+ *
+ * pli_attn_decode_paged_mxfp4: pli_attn_decode_paged_fp8 with the scale pools
+ *   in place of k_scale / v_scale and exp_strides after strides; workspace from
+ *   pli_attn_decode_paged_workspace_size, the split plan the 16-bit call's.
+ *   The MFMA kernel attn_decode_paged_mxfp4 takes what attn_decode_paged_fp8
+ *   takes (bf16 / fp16 q, head_dim 64 / 128, at most 16 rows per kv head, a
+ *   power-of-two block_size >= 16, scale > 0, code-pool strides multiples of 16
+ *   bytes, q / o strides multiples of 8, 16-byte aligned q, o and code pools);
+ *   a lane's 16-byte load is one block of 32 codes.  pli_last_route:
+ *   "attn_decode_paged_mxfp4",
+ *   "attn_decode_paged_mxfp4+attn_decode_paged_combine" or
+ *   "attn_decode_paged_generic_mxfp4" (fp32 q, any head_dim % 32 == 0 up to
+ *   256, any block_size and group size; it decodes with csrc/fp4_codec.h).
+ * pli_kv_append_paged_mxfp4 / pli_kv_append_varlen_paged_mxfp4: positions,
+ *   drops and clamps of pli_kv_append_paged / pli_kv_append_varlen_paged;
+ *   `dtype` is the source's (fp32 / fp16 / bf16).  strides as there, the
+ *   source's in its elements (multiples of 8), the code pools' in bytes
+ *   (multiples of 4); sources and code pools 16-byte aligned.  pli_last_route:
+ *   "kv_append_paged_mxfp4" / "kv_append_varlen_paged_mxfp4".
+ * PLI_EINVAL before any HIP call, in the order of the fp8 calls, plus:
+ *   head_dim % 32 != 0 (after the dtype check), a NULL scale pool or
+ *   exp_strides on a non-empty call (with the other null pointers), a scale
+ *   stride below head_dim / 32 (after the empty-pool check).  Empty calls
+ *   return PLI_OK and may pass NULL operands.  Nothing is allocated or
+ *   synchronised; tables, lengths, codes and scale bytes are read on the
+ *   device, so a captured call replays while they change in place. */
+int pli_attn_decode_paged_mxfp4(const void* q, const void* k_pool,
+                                const void* v_pool, void* o,
+                                const int32_t* block_table,
+                                const int32_t* seq_lens,
+                                const void* k_exp_pool, const void* v_exp_pool,
+                                int batch, int heads, int kv_heads, int n_q,
+                                int head_dim, int block_size, int num_blocks,
+                                int max_blocks_per_seq, int max_kv,
+                                const int64_t* strides,
+                                const int64_t* exp_strides, float scale,
+                                int causal, int n_kv_add, void* workspace,
+                                size_t workspace_bytes, int dtype,
+                                void* stream);
+int pli_kv_append_paged_mxfp4(const void* k_new, const void* v_new,
+                              void* k_pool, void* v_pool, void* k_exp_pool,
+                              void* v_exp_pool, const int32_t* block_table,
+                              const int32_t* seq_lens, int batch, int n_new,
+                              int kv_heads, int head_dim, int block_size,
+                              int num_blocks, int max_blocks_per_seq,
+                              const int64_t* strides,
+                              const int64_t* exp_strides, int dtype,
+                              void* stream);
+int pli_kv_append_varlen_paged_mxfp4(const void* k_new, const void* v_new,
+                                     void* k_pool, void* v_pool,
+                                     void* k_exp_pool, void* v_exp_pool,
+                                     const int32_t* cu_seqlens_q,
+                                     const int32_t* block_table,
+                                     const int32_t* seq_lens, int batch,
+                                     int max_tokens, int kv_heads,
+                                     int head_dim, int block_size,
+                                     int num_blocks, int max_blocks_per_seq,
+                                     const int64_t* strides,
+                                     const int64_t* exp_strides, int dtype,
+                                     void* stream);
+
 /* Split-K for the packed calls: pli_attn_varlen_paged / _fp8 with a caller
  * workspace.  The plain calls give a 64-row tile one workgroup that walks all
  * of the tile's keys; these cut the tile's key range [0, key_end) into chunks

@@ -33,7 +33,7 @@ CFLAGS = ["-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", f"--offload-arch=
 # per-source extra flags.  flash_v7: no NaN ever reaches the softmax (masks
 # use -inf), so fmaxf on MFMA results folds into v_max3_f32 without the
 # canonicalising v_max_f32 hipcc otherwise puts in front of each one.
-# linear_mxfp4w, gemm_mxfp4, gemm_mx_splitk, gemm_grouped_mxfp4, gemm_grouped_mxfp4_splitk, gemm_mxfp4_a4, quant_mxfp4, gemm_grouped_mxfp4_a4: built without the packed-fp32 VALU forms (v_pk_{add,mul,fma}_f32), a
+# linear_mxfp4w, gemm_mxfp4, gemm_mx_splitk, gemm_grouped_mxfp4, gemm_grouped_mxfp4_splitk, gemm_mxfp4_a4, quant_mxfp4, gemm_grouped_mxfp4_a4, paged_attn_mxfp4: built without the packed-fp32 VALU forms (v_pk_{add,mul,fma}_f32), a
 # standing requirement of the hosts this project is verified on for new HIP
 # sources (older sources stay as they were validated).  Its whole effect here:
 # the v_pk_add_f32 / v_pk_mul_f32 of the epilogue reductions become the scalar
@@ -42,7 +42,8 @@ NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA = {"flash_v7.hip": ["-fno-honor-nans"], "flash_v12.hip": ["-fno-honor-nans"],
          "linear_mxfp4w.hip": NO_PK_F32, "gemm_mxfp4.hip": NO_PK_F32, "gemm_mx_splitk.hip": NO_PK_F32,
          "gemm_grouped_mxfp4.hip": NO_PK_F32, "gemm_grouped_mxfp4_splitk.hip": NO_PK_F32,
-         "gemm_mxfp4_a4.hip": NO_PK_F32, "quant_mxfp4.hip": NO_PK_F32, "gemm_grouped_mxfp4_a4.hip": NO_PK_F32}
+         "gemm_mxfp4_a4.hip": NO_PK_F32, "quant_mxfp4.hip": NO_PK_F32, "gemm_grouped_mxfp4_a4.hip": NO_PK_F32,
+         "paged_attn_mxfp4.hip": NO_PK_F32}
 
 
 def hipcc() -> str:

@@ -31,6 +31,13 @@ OCP fp8 e4m3 codes with one fp32 scale per (layer, kv head) for K and for V
 (``k_scale`` / ``v_scale``, ones until ``set_scales``): the same four methods
 then quantise on append and attend through the ``*_fp8`` entry points, and the
 same memory holds twice the tokens.
+
+``PagedKVCache(..., kv_dtype=torch.float4_e2m1fn_x2)`` keeps them as MXFP4: uint8
+code pools (two e2m1 codes per byte) plus ``k_exp_cache`` / ``v_exp_cache``, one
+E8M0 scale byte per 32 elements, no per-head scales.  ``append``,
+``append_packed`` and ``attend`` go through the ``*_mxfp4`` entry points; packed
+attention over such a pool is not provided (``attend_packed`` and the packed
+workspace methods raise ``NotImplementedError``).
 """
 from __future__ import annotations
 
@@ -40,6 +47,10 @@ from dataclasses import dataclass, field
 import torch
 
 import pli_hip
+
+
+# the selector of an MXFP4 cache; no tensor of this dtype is made, the pools are uint8
+MXFP4 = torch.float4_e2m1fn_x2
 
 
 @dataclass
@@ -60,8 +71,8 @@ class _CacheOptions(type):
     call of the class, and is on the instance before ``__init__`` runs."""
 
     def __call__(cls, *args, kv_dtype: torch.dtype | None = None, **kwargs):
-        if kv_dtype not in (None, torch.float8_e4m3fn):
-            raise ValueError(f"kv_dtype must be None or torch.float8_e4m3fn, got {kv_dtype}")
+        if kv_dtype not in (None, torch.float8_e4m3fn, MXFP4):
+            raise ValueError(f"kv_dtype must be None, torch.float8_e4m3fn or torch.float4_e2m1fn_x2, got {kv_dtype}")
         self = cls.__new__(cls)
         self.kv_dtype = kv_dtype
         self.__init__(*args, **kwargs)
@@ -101,16 +112,34 @@ class PagedKVCache(metaclass=_CacheOptions):
 
         # the pools exist only on a device (None otherwise, as in the reference)
         self.k_cache = self.v_cache = None
+        # MXFP4 pools: uint8 code pools (two e2m1 codes per byte) and, in k_exp_cache / v_exp_cache, one E8M0 byte
+        # per 32 elements: value = decode(code) * 2^(exp - 127), no per-head scales
+        self.k_exp_cache = self.v_exp_cache = None
+        if kv_dtype is MXFP4 and head_dim % 32:
+            raise ValueError(f"an MXFP4 cache (kv_dtype={MXFP4}) needs head_dim % 32 == 0, got {head_dim}")
         on_device = torch.cuda.is_available() and torch.device(device).type == "cuda"
         if on_device:
-            shape = (num_blocks, num_layers, block_size, num_heads, head_dim)
-            self.k_cache = torch.zeros(shape, dtype=kv_dtype or dtype, device=device)
-            self.v_cache = torch.zeros(shape, dtype=kv_dtype or dtype, device=device)
+            shape, exp_shape = self.pool_shapes()
+            pool_dtype = torch.uint8 if kv_dtype is MXFP4 else kv_dtype or dtype
+            self.k_cache = torch.zeros(shape, dtype=pool_dtype, device=device)
+            self.v_cache = torch.zeros(shape, dtype=pool_dtype, device=device)
+            if kv_dtype is MXFP4:
+                # byte 127 is the scale 1.0: an empty pool decodes to zeros
+                self.k_exp_cache = torch.full(exp_shape, 127, dtype=torch.uint8, device=device)
+                self.v_exp_cache = torch.full(exp_shape, 127, dtype=torch.uint8, device=device)
         # fp8 pools: value = code * scale[layer, kv head]; the scales live where the pools do (host copies off-device)
         self.k_scale = self.v_scale = None
-        if kv_dtype is not None:
+        if kv_dtype is torch.float8_e4m3fn:
             self.k_scale = torch.ones(num_layers, num_heads, dtype=torch.float32, device=device if on_device else "cpu")
             self.v_scale = torch.ones_like(self.k_scale)
+
+    def pool_shapes(self):
+        """(shape of k_cache / v_cache, shape of k_exp_cache / v_exp_cache or None): an MXFP4 cache keeps
+        head_dim / 2 code bytes and head_dim / 32 scale bytes per (token, kv head)"""
+        lead = (self.num_blocks, self.num_layers, self.block_size, self.num_heads)
+        if self.kv_dtype is MXFP4:
+            return lead + (self.head_dim // 2,), lead + (self.head_dim // 32,)
+        return lead + (self.head_dim,), None
 
     # ------------------------------------------------------------ allocator --
     def _blocks_for(self, num_tokens: int) -> int:
@@ -151,8 +180,10 @@ class PagedKVCache(metaclass=_CacheOptions):
         free = len(self.free_blocks)
         used = self.num_blocks - free
         # K and V, every layer, 2 bytes per element (the reference's fp16 figure), 1 for an fp8 cache
-        elem_bytes = 2 if self.kv_dtype is None else 1
-        bytes_per_block = 2 * self.num_layers * self.block_size * self.num_heads * self.head_dim * elem_bytes
+        # an MXFP4 one: head_dim / 2 code bytes + head_dim / 32 scale bytes per row
+        row_bytes = {None: 2 * self.head_dim, MXFP4: self.head_dim // 2 + self.head_dim // 32}.get(self.kv_dtype,
+                                                                                                   self.head_dim)
+        bytes_per_block = 2 * self.num_layers * self.block_size * self.num_heads * row_bytes
         mb = 1024 * 1024
         return {
             "total_blocks": self.num_blocks,
@@ -174,12 +205,20 @@ class PagedKVCache(metaclass=_CacheOptions):
         # [num_blocks, block_size, heads, head_dim] views: the layer is in the page stride
         return self.k_cache[:, layer], self.v_cache[:, layer]
 
+    def _exp_pools(self, layer: int):
+        return self.k_exp_cache[:, layer], self.v_exp_cache[:, layer]
+
+    def _no_packed_attention(self, what: str) -> None:
+        if self.kv_dtype is MXFP4:
+            raise NotImplementedError(f"{what}: packed (varlen) attention over an MXFP4 pool is not provided "
+                                      f"(kv_dtype={MXFP4}); attend() serves decode steps")
+
     def set_scales(self, layer: int, k_scale, v_scale) -> None:
         """Set an fp8 cache's per-kv-head scales of one layer, in place (so a
         captured graph sees them): each a tensor or sequence of num_heads
         finite values > 0.  Tokens already in the pool keep the codes they were
         stored with."""
-        if self.kv_dtype is None:
+        if self.kv_dtype is not torch.float8_e4m3fn:
             raise ValueError("set_scales needs an fp8 cache (kv_dtype=torch.float8_e4m3fn)")
         if not 0 <= layer < self.num_layers:
             raise IndexError(f"layer {layer} outside [0, {self.num_layers})")
@@ -218,6 +257,9 @@ class PagedKVCache(metaclass=_CacheOptions):
         count the new tokens."""
         k_pool, v_pool = self._pools(layer)
         start = seq_lens - k_new.shape[1]
+        if self.kv_dtype is MXFP4:
+            pli_hip.kv_append_paged_mxfp4(k_new, v_new, k_pool, v_pool, *self._exp_pools(layer), block_table, start)
+            return
         if self.kv_dtype is not None:
             pli_hip.kv_append_paged_fp8(k_new, v_new, k_pool, v_pool, block_table, start, self.k_scale[layer],
                                         self.v_scale[layer])
@@ -230,6 +272,9 @@ class PagedKVCache(metaclass=_CacheOptions):
         seq_lens[b] + n_kv_add tokens of this layer's pages, read in place;
         causal masks bottom-right per sequence.  Returns [B, Sq, Hq, head_dim]."""
         k_pool, v_pool = self._pools(layer)
+        if self.kv_dtype is MXFP4:
+            return pli_hip.attn_decode_paged_mxfp4(q, k_pool, v_pool, *self._exp_pools(layer), block_table, seq_lens,
+                                                   causal=causal, n_kv_add=n_kv_add)
         if self.kv_dtype is not None:
             return pli_hip.attn_decode_paged_fp8(q, k_pool, v_pool, block_table, seq_lens, self.k_scale[layer],
                                                  self.v_scale[layer], causal=causal, n_kv_add=n_kv_add)
@@ -258,6 +303,10 @@ class PagedKVCache(metaclass=_CacheOptions):
         tokens of their sequences: row cu[b] + i goes to position
         seq_lens[b] - (cu[b+1] - cu[b]) + i."""
         k_pool, v_pool = self._pools(layer)
+        if self.kv_dtype is MXFP4:
+            pli_hip.kv_append_varlen_paged_mxfp4(k_new, v_new, k_pool, v_pool, *self._exp_pools(layer), block_table,
+                                                 seq_lens, cu_seqlens_q)
+            return
         if self.kv_dtype is not None:
             pli_hip.kv_append_varlen_paged_fp8(k_new, v_new, k_pool, v_pool, block_table, seq_lens, cu_seqlens_q,
                                                self.k_scale[layer], self.v_scale[layer])
@@ -270,7 +319,8 @@ class PagedKVCache(metaclass=_CacheOptions):
         over tables ``max_blocks`` wide (default: the whole pool): the size
         pli_attn_varlen_paged_workspace_size reports, 0 when the keys are too
         few to split."""
-        width = self.num_blocks if max_blocks is None else int(max_blocks)
+        self._no_packed_attention("packed_workspace_bytes")
+        width =self.num_blocks if max_blocks is None else int(max_blocks)
         return pli_hip.attn_varlen_paged_workspace_bytes(batch, max_tokens, q_heads, self.num_heads,
                                                          width * self.block_size, self.head_dim)
 
@@ -278,6 +328,7 @@ class PagedKVCache(metaclass=_CacheOptions):
         """A float32 device tensor of ``packed_workspace_bytes(...)`` bytes (at
         least one element) for ``attend_packed``; it need not be initialised
         and can be reused by every layer and step of the same sizes."""
+        self._no_packed_attention("packed_workspace")
         if self.k_cache is None:
             raise pli_hip.PliError("PagedKVCache has no device pools (created off-device)")
         need = self.packed_workspace_bytes(batch, max_tokens, q_heads, max_blocks)
@@ -287,6 +338,7 @@ class PagedKVCache(metaclass=_CacheOptions):
                           cu_seqlens_q: torch.Tensor, causal: bool = True, *, workspace: torch.Tensor) -> torch.Tensor:
         """attend_packed through the split-K calls (pli_attn_varlen_paged_ws /
         _fp8_ws) with the plan's own span"""
+        self._no_packed_attention("attend_packed")
         k_pool, v_pool = self._pools(layer)
         if self.kv_dtype is not None:
             return pli_hip.attn_varlen_paged_fp8(q, k_pool, v_pool, block_table, seq_lens, cu_seqlens_q,
@@ -304,6 +356,7 @@ class PagedKVCache(metaclass=_CacheOptions):
         head_dim].  The keyword ``workspace=`` (a ``packed_workspace(...)``
         tensor; default None, this call as it is) makes the split-K call, which
         gives a long sequence's tile several workgroups."""
+        self._no_packed_attention("attend_packed")
         k_pool, v_pool = self._pools(layer)
         if self.kv_dtype is not None:
             return pli_hip.attn_varlen_paged_fp8(q, k_pool, v_pool, block_table, seq_lens, cu_seqlens_q,
@@ -355,6 +408,16 @@ A 1-byte cache (kv_dtype=torch.float8_e4m3fn):
     global load and the LDS write, so the MFMA loop and the softmax are those of
     the 16-bit kernels, with k_scale folded into the softmax constant and
     v_scale into the final 1/l.
+
+An MXFP4 cache (kv_dtype=torch.float4_e2m1fn_x2):
+  - The pools hold e2m1 codes, two per byte, and a scale pool holds one E8M0
+    byte per 32 elements of a row: 68 bytes per (token, kv head) at head_dim
+    128 against 128 for fp8 -- 1.88x the tokens in the same HBM.
+  - The appends quantise each block of 32 exactly (power-of-two scale,
+    round to nearest even); pli_attn_decode_paged_mxfp4 widens a block with
+    its scale folded in between a 16-byte load and the LDS write, and the
+    MFMA loop is the 16-bit kernel's.  append / append_packed / attend work;
+    packed attention over such a pool is not provided.
 """
 
 

@@ -36,6 +36,7 @@
 #include <cmath>
 
 #include "fp8_kv.h"
+#include "paged_combine.h"
 #include "paged_plan.h"
 #include "pli_common.h"
 
@@ -798,6 +799,27 @@ int launch_append_fp8(const char* kn, const char* vn, char* kpool, char* vpool, 
 }
 
 }  // namespace
+
+// the combine kernel for paged_attn_mxfp4.hip (paged_combine.h)
+void launch_paged_combine(int dtype, int head_dim, const float* part_o, const void* part_ml, void* o, int batch,
+                          int kv_heads, int group, int rows, int64_t o_b, int64_t o_h, int64_t o_n, int splits,
+                          hipStream_t stream) {
+    PagedStrides st{};
+    st.ob = o_b, st.oh = o_h, st.on = o_n;
+    const dim3 grid((unsigned)((int64_t)batch * kv_heads * rows));
+#define PLI_PAGED_COMBINE(T, D)                                                                                   \
+    hipLaunchKernelGGL((attn_decode_paged_combine<T, D>), grid, dim3(256), 0, stream, part_o, (const float2*)part_ml, \
+                       (uint16_t*)o, kv_heads, group, rows, st, splits)
+    if (dtype == PLI_BF16) {
+        if (head_dim == 128) PLI_PAGED_COMBINE(bf16_t, 128);
+        else PLI_PAGED_COMBINE(bf16_t, 64);
+    } else {
+        if (head_dim == 128) PLI_PAGED_COMBINE(f16_t, 128);
+        else PLI_PAGED_COMBINE(f16_t, 64);
+    }
+#undef PLI_PAGED_COMBINE
+}
+
 }  // namespace pli
 
 extern "C" size_t pli_attn_decode_paged_workspace_size(int batch, int heads, int kv_heads, int n_q,

@@ -95,6 +95,30 @@ PLI_HD inline int64_t paged_key_offset(const int32_t* table, int b, int j, int h
     return paged_offset(paged_page_of(table, b, paged_block_of(j, t), t), j, hk, t, p);
 }
 
+// ---- MXFP4 pools ----------------------------------------------------------------
+// A code pool (head_dim / 2 bytes per row, strides in bytes) goes through the
+// functions above.  Its scale pool is a byte pool of its own with its own
+// {page, token, head} strides: row (page, slot, head) holds head_dim / 32
+// contiguous E8M0 bytes, byte `blk` covering elements [32 blk, 32 blk + 32).
+// The row is found exactly as the code row is, so the clamps are shared.
+PLI_HD inline int64_t paged_exp_offset(int page, int j, int hk, int blk, const PagedTable& t, const PagedPool& e) {
+    return paged_offset(page, j, hk, t, e) + blk;
+}
+PLI_HD inline int64_t paged_exp_offset_pow2(int page, int j, int hk, int blk, const PagedTable& t,
+                                            const PagedPool& e) {
+    return paged_offset_pow2(page, j, hk, t, e) + blk;
+}
+PLI_HD inline int64_t paged_exp_key_offset(const int32_t* table, int b, int j, int hk, int blk, const PagedTable& t,
+                                           const PagedPool& e) {
+    return paged_key_offset(table, b, j, hk, t, e) + blk;
+}
+// every scale-pool stride holds a row's head_dim / 32 bytes
+PLI_HD inline bool paged_exp_strides_ok(const int64_t* exp_strides6, int head_dim) {
+    for (int i = 0; i < 6; ++i)
+        if (exp_strides6[i] < head_dim / 32) return false;
+    return true;
+}
+
 // valid keys of a sequence: clamp(seq_lens[b] + n_kv_add, 0, max_kv)
 PLI_HD inline int paged_seq_len(int seq_len, int n_kv_add, int max_kv) {
     const int64_t n = (int64_t)seq_len + n_kv_add;
@@ -131,6 +155,15 @@ inline bool paged_fast_path_fp8(int dtype, int head_dim, int64_t rows_per_kv_hea
     for (int i = 3; i < 9; ++i)
         if (strides12[i] % 16 != 0) return false;
     return true;
+}
+
+// And for an MXFP4 pool, attn_decode_paged_mxfp4: a 16-byte load is one block
+// of 32 codes, so the code-pool strides (in bytes) are multiples of 16 as the
+// fp8 pool's are and head_dim 64 / 128 are rows of 2 / 4 loads; the scale
+// pools are read by the byte and add no condition.
+inline bool paged_fast_path_mxfp4(int dtype, int head_dim, int64_t rows_per_kv_head, int block_size, float scale,
+                                  const int64_t* strides12, bool aligned16_operands) {
+    return paged_fast_path_fp8(dtype, head_dim, rows_per_kv_head, block_size, scale, strides12, aligned16_operands);
 }
 
 // ---- split-K plan -----------------------------------------------------------

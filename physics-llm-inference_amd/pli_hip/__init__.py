@@ -99,6 +99,11 @@ _SIGS = {
                                   _c_int, _vp],
     "pli_kv_append_varlen_paged_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int,
                                        _c_int, _c_int, _c_int, ctypes.POINTER(_c_i64), _c_int, _vp],
+    # MXFP4 pools: k_exp_pool, v_exp_pool in place of the fp8 scales, exp_strides[6] after strides
+    "pli_attn_decode_paged_mxfp4": [_vp] * 8 + [_c_int] * 9 + [ctypes.POINTER(_c_i64)] * 2 +
+                                   [_c_f32, _c_int, _c_int, _vp, ctypes.c_size_t, _c_int, _vp],
+    "pli_kv_append_paged_mxfp4": [_vp] * 8 + [_c_int] * 7 + [ctypes.POINTER(_c_i64)] * 2 + [_c_int, _vp],
+    "pli_kv_append_varlen_paged_mxfp4": [_vp] * 9 + [_c_int] * 7 + [ctypes.POINTER(_c_i64)] * 2 + [_c_int, _vp],
     # split-K packed calls: the plain signatures plus split_keys, workspace, workspace_bytes before the stream
     "pli_attn_varlen_paged_workspace_size": [_c_int] * 7,
     "pli_attn_varlen_paged_split_plan": [_c_int] * 7 + [ctypes.POINTER(_c_int), ctypes.POINTER(_c_int)],
@@ -852,6 +857,136 @@ def kv_append_varlen_paged_fp8(k_new: torch.Tensor, v_new: torch.Tensor, k_pool:
                                                   num_blocks, block_table.shape[1], st, _dtype_code(k_new),
                                                   _stream(dev))
     _check(rc, "pli_kv_append_varlen_paged_fp8")
+
+
+# ------------------------------------------------------ MXFP4 paged KV cache
+def _check_mxfp4_kv(what: str, x: torch.Tensor, pools, ints: dict):
+    """shared checks of the MXFP4 KV calls: x (q or k_new) fp32 / fp16 / bf16 with D last, D % 32 == 0; pools =
+    (k_pool, v_pool, k_exp_pool, v_exp_pool), uint8 views [num_blocks, block_size, Hkv, D / 2] of codes and
+    [num_blocks, block_size, Hkv, D / 32] of E8M0 bytes (any page stride, unit inner stride); the named int32 tensors
+    contiguous; returns the device"""
+    dev = _require_gpu(x)
+    _dtype_code(x)
+    k_pool, v_pool, k_exp, v_exp = pools
+    for name, t in zip(("k_pool", "v_pool", "k_exp_pool", "v_exp_pool"), pools):
+        if not t.is_cuda or t.device != dev or t.dtype != torch.uint8:
+            raise PliError(f"{what}: {name} must be a torch.uint8 tensor on {dev}, got {t.dtype} on {t.device}")
+    for name, t in ints.items():
+        if not t.is_cuda or t.device != dev or t.dtype != torch.int32 or not t.is_contiguous():
+            raise PliError(f"{what}: {name} must be a contiguous int32 tensor on {dev}")
+    D = x.shape[-1]
+    if D % 32 or k_pool.dim() != 4 or tuple(v_pool.shape) != tuple(k_pool.shape) or k_pool.shape[3] != D // 2 or \
+            tuple(k_exp.shape) != tuple(k_pool.shape[:3]) + (D // 32,) or tuple(v_exp.shape) != tuple(k_exp.shape):
+        raise PliError(f"{what} expects head_dim % 32 == 0, [num_blocks, block_size, Hkv, D / 2] code pools and "
+                       f"[num_blocks, block_size, Hkv, D / 32] scale pools, got {tuple(x.shape)} k{tuple(k_pool.shape)} "
+                       f"v{tuple(v_pool.shape)} k_exp{tuple(k_exp.shape)} v_exp{tuple(v_exp.shape)}")
+    if any(t.stride(-1) != 1 for t in (x,) + tuple(pools) if t.numel()):
+        raise PliError(f"{what}: a unit inner stride is required (the pools are used in place)")
+    return dev
+
+
+def _pool_strides(k: torch.Tensor, v: torch.Tensor):
+    return [int(t.stride(i)) for t in (k, v) for i in range(3)]
+
+
+def attn_decode_paged_mxfp4(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, k_exp_pool: torch.Tensor,
+                            v_exp_pool: torch.Tensor, block_table: torch.Tensor, seq_lens: torch.Tensor, *,
+                            scale: float | None = None, causal: bool = True, n_kv_add: int = 0,
+                            max_kv: int | None = None, out: torch.Tensor | None = None,
+                            workspace: torch.Tensor | None = None) -> torch.Tensor:
+    """attn_decode_paged over MXFP4 pools: uint8 code pools [num_blocks, block_size, Hkv, D / 2] (two e2m1 codes per
+    byte) and uint8 scale pools [num_blocks, block_size, Hkv, D / 32] (one E8M0 byte per 32 elements), value =
+    decode(code) * 2^(exp - 127); codes and scale bytes are read on the device (graph-replayable).  q and the output
+    are bf16 / fp16 (MFMA kernel) or fp32."""
+    dev = _check_mxfp4_kv("attn_decode_paged_mxfp4", q, (k_pool, v_pool, k_exp_pool, v_exp_pool),
+                          {"block_table": block_table, "seq_lens": seq_lens})
+    if q.dim() != 4 or block_table.dim() != 2 or block_table.shape[0] != q.shape[0] or \
+            tuple(seq_lens.shape) != (q.shape[0],):
+        raise PliError(f"attn_decode_paged_mxfp4: shape mismatch q{tuple(q.shape)} table{tuple(block_table.shape)} "
+                       f"seq_lens{tuple(seq_lens.shape)}")
+    B, Sq, H, D = q.shape
+    num_blocks, bs, Hkv, _ = k_pool.shape
+    max_blocks = block_table.shape[1]
+    if Hkv == 0 or H % Hkv != 0:
+        raise PliError(f"heads {H} not a multiple of kv heads {Hkv}")
+    cap = max_blocks * bs
+    max_kv = cap if max_kv is None else int(max_kv)
+    if not 0 <= max_kv <= cap:
+        raise PliError(f"max_kv {max_kv} outside the table row [0, {cap}]")
+    if out is None:
+        out = torch.empty((B, Sq, H, D), device=q.device, dtype=q.dtype)
+    _require_gpu(q, out)
+    if tuple(out.shape) != (B, Sq, H, D) or (out.numel() and out.stride(-1) != 1):
+        raise PliError("bad output tensor")
+    if scale is None:
+        scale = D ** -0.5
+    st = (_c_i64 * 12)(*([int(x) for x in (q.stride(0), q.stride(2), q.stride(1))] + _pool_strides(k_pool, v_pool) +
+                         [int(x) for x in (out.stride(0), out.stride(2), out.stride(1))]))
+    est = (_c_i64 * 6)(*_pool_strides(k_exp_pool, v_exp_pool))
+    ws_bytes = int(lib().pli_attn_decode_paged_workspace_size(B, H, Hkv, Sq, max_kv, D))
+    if workspace is None or workspace.numel() * workspace.element_size() < ws_bytes:
+        workspace = torch.empty(max(ws_bytes // 4, 1), device=q.device, dtype=torch.float32)
+    with _on_device(dev):
+        rc = lib().pli_attn_decode_paged_mxfp4(_ptr(q), _ptr(k_pool), _ptr(v_pool), _ptr(out), _ptr(block_table),
+                                               _ptr(seq_lens), _ptr(k_exp_pool), _ptr(v_exp_pool), B, H, Hkv, Sq, D, bs,
+                                               num_blocks, max_blocks, max_kv, st, est, float(scale),
+                                               int(bool(causal)), int(n_kv_add), _ptr(workspace), ws_bytes,
+                                               _dtype_code(q), _stream(dev))
+    _check(rc, "pli_attn_decode_paged_mxfp4")
+    return out
+
+
+def kv_append_paged_mxfp4(k_new: torch.Tensor, v_new: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor,
+                          k_exp_pool: torch.Tensor, v_exp_pool: torch.Tensor, block_table: torch.Tensor,
+                          seq_lens: torch.Tensor) -> None:
+    """kv_append_paged into MXFP4 pools: every block of 32 elements of k_new / v_new [B, T, Hkv, D] (fp32 / fp16 /
+    bf16) is stored as 32 e2m1 codes and one E8M0 byte, bit for bit quantize_weight_mxfp4(rows, torch.float16)."""
+    pools = (k_pool, v_pool, k_exp_pool, v_exp_pool)
+    dev = _check_mxfp4_kv("kv_append_paged_mxfp4", k_new, pools, {"block_table": block_table, "seq_lens": seq_lens})
+    _require_gpu(k_new, v_new)
+    if k_new.dim() != 4 or tuple(v_new.shape) != tuple(k_new.shape) or k_pool.shape[2] != k_new.shape[2] or \
+            (v_new.numel() and v_new.stride(-1) != 1) or block_table.dim() != 2 or \
+            block_table.shape[0] != k_new.shape[0] or tuple(seq_lens.shape) != (k_new.shape[0],):
+        raise PliError(f"kv_append_paged_mxfp4 shape mismatch new{tuple(k_new.shape)} v{tuple(v_new.shape)} "
+                       f"pool{tuple(k_pool.shape)} table{tuple(block_table.shape)} seq_lens{tuple(seq_lens.shape)}")
+    B, T, Hkv, D = k_new.shape
+    st = (_c_i64 * 12)(*([int(x) for x in (k_new.stride(0), k_new.stride(2), k_new.stride(1))] +
+                         _pool_strides(k_pool, v_pool) +
+                         [int(x) for x in (v_new.stride(0), v_new.stride(2), v_new.stride(1))]))
+    est = (_c_i64 * 6)(*_pool_strides(k_exp_pool, v_exp_pool))
+    with _on_device(dev):
+        rc = lib().pli_kv_append_paged_mxfp4(_ptr(k_new), _ptr(v_new), *(_ptr(p) for p in pools), _ptr(block_table),
+                                             _ptr(seq_lens), B, T, Hkv, D, k_pool.shape[1], k_pool.shape[0],
+                                             block_table.shape[1], st, est, _dtype_code(k_new), _stream(dev))
+    _check(rc, "pli_kv_append_paged_mxfp4")
+
+
+def kv_append_varlen_paged_mxfp4(k_new: torch.Tensor, v_new: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor,
+                                 k_exp_pool: torch.Tensor, v_exp_pool: torch.Tensor, block_table: torch.Tensor,
+                                 seq_lens: torch.Tensor, cu_seqlens_q: torch.Tensor) -> None:
+    """kv_append_varlen_paged into MXFP4 pools (packed k_new / v_new [tokens, Hkv, D]); quantisation as for
+    kv_append_paged_mxfp4."""
+    pools = (k_pool, v_pool, k_exp_pool, v_exp_pool)
+    dev = _check_mxfp4_kv("kv_append_varlen_paged_mxfp4", k_new, pools,
+                          {"block_table": block_table, "seq_lens": seq_lens, "cu_seqlens_q": cu_seqlens_q})
+    _require_gpu(k_new, v_new)
+    B = seq_lens.shape[0] if seq_lens.dim() == 1 else -1
+    if k_new.dim() != 3 or tuple(v_new.shape) != tuple(k_new.shape) or k_pool.shape[2] != k_new.shape[1] or \
+            (v_new.numel() and v_new.stride(-1) != 1) or block_table.dim() != 2 or block_table.shape[0] != B or \
+            tuple(cu_seqlens_q.shape) != (B + 1,):
+        raise PliError(f"kv_append_varlen_paged_mxfp4 shape mismatch new{tuple(k_new.shape)} v{tuple(v_new.shape)} "
+                       f"pool{tuple(k_pool.shape)} table{tuple(block_table.shape)} seq_lens{tuple(seq_lens.shape)} "
+                       f"cu_seqlens_q{tuple(cu_seqlens_q.shape)}")
+    T, Hkv, D = k_new.shape
+    st = (_c_i64 * 10)(*([int(k_new.stride(0)), int(k_new.stride(1))] + _pool_strides(k_pool, v_pool) +
+                         [int(v_new.stride(0)), int(v_new.stride(1))]))
+    est = (_c_i64 * 6)(*_pool_strides(k_exp_pool, v_exp_pool))
+    with _on_device(dev):
+        rc = lib().pli_kv_append_varlen_paged_mxfp4(_ptr(k_new), _ptr(v_new), *(_ptr(p) for p in pools),
+                                                    _ptr(cu_seqlens_q), _ptr(block_table), _ptr(seq_lens), B, T, Hkv,
+                                                    D, k_pool.shape[1], k_pool.shape[0], block_table.shape[1], st, est,
+                                                    _dtype_code(k_new), _stream(dev))
+    _check(rc, "pli_kv_append_varlen_paged_mxfp4")
 
 
 # ---------------------------------------------------------------------- MoE
